@@ -18,6 +18,9 @@ per transition: DESIGN.md 8); a short burn-in times a transient that is 30 times
 compares the leapfrogs per iteration of the timed window with those of the next `--mode-iters` iterations of the same chain and says
 whether they agree within 20 %; `value` is only a stationary figure when it says so.
 
+`--dump-outputs DIR` writes what the last timed iteration returned (dump_outputs) as .npy files: the inputs and seeds depend on the
+arguments alone, so two builds can be compared output for output.
+
 Extra objects on the same JSON line:
   roofline            dominant kernel of the sweep, HIP-event timing on the sampler's own stream, against 8 TB/s HBM
   per_chain_hmc_mode1 the same chain continued for K more timed iterations with one O(N) device evaluation per leapfrog
@@ -309,6 +312,35 @@ def reference_r_leg(n, p, trees, iters):
     return {"status": "bench/reference_cpu.R did not report (is the stan4bart package installed?): " + out.stderr.strip()[-300:], "script": "bench/reference_cpu.R"}
 
 
+DUMP_MAX_BYTES = 64 << 20     # all files of --dump-outputs together, over all ranks
+
+
+def dump_outputs(out_dir, out, rank, world):
+    """`--dump-outputs DIR`: what the timed path returned for its LAST step (stan4bart_run with keep_fits off hands back that one
+    column): the Stan parameter row, sigma, the train / test fits, the predictor use counts and, when k is modeled, k, written as
+    float64 `.npy` files — `<name>.npy` at N = 1, `<name>_chain<rank>.npy` for every chain at N > 1.  A fit vector too large for the
+    byte budget is replaced by a fixed, seeded sample of its rows (`<name>_rows` holds their indices, also float64)."""
+    sfx = f"_chain{rank}" if world > 1 else ""
+    small = {"stan": out["stan"][:, -1], "bart_sigma": out["bart"]["sigma"][-1:], "bart_varcount": out["bart"]["varcount"][:, -1]}
+    if "k" in out["bart"]:
+        small["bart_k"] = out["bart"]["k"][-1:]
+    big = {k: v[:, -1] for k, v in (("bart_train", out["bart"]["train"]), ("bart_test", out["bart"]["test"])) if v.size}
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in small.items()}
+    budget = DUMP_MAX_BYTES // world - sum(v.nbytes for v in arrays.values()) - 4096 * (len(small) + 2 * len(big))
+    total = sum(v.size for v in big.values())
+    for name, v in big.items():
+        v = np.asarray(v, dtype=np.float64)
+        if total * 8 > budget:
+            m = min(v.size, int(budget * v.size / total) // 16)          # 8 B value + 8 B row index
+            rows = np.sort(np.random.default_rng(20260101).choice(v.size, size=m, replace=False))
+            arrays[name + "_rows"] = rows.astype(np.float64)
+            v = v[rows]
+        arrays[name] = v
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), np.ascontiguousarray(v))
+
+
 def self_launch(a, argv):
     """`python bench.py --gpus N` (N > 1) without a launcher: the chain fan-out of the reference (R/stan4bart_fit.R:498-533 starts one
     worker process per chain) needs one process per GPU, so this process — BEFORE any GPU call — starts
@@ -365,9 +397,13 @@ def main():
     ap.add_argument("--emul", action="store_true",
                     help="TEST ONLY (pytest -m 'not gpu'): run the N-rank plumbing of this script over the CPU emulation of the device layer "
                          "(tests/emul) and gloo; prints a line whose numbers mean nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its last step to DIR/<name>.npy (float64, 64 MB at most)")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(a, sys.argv[1:])
     t_start = time.perf_counter()
@@ -440,6 +476,8 @@ def main():
     dt = time.perf_counter() - t0
     c1, s1 = sampler.get_counters(), sampler.get_nuts_stats()
     barrier()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, rank, world)
     hmc_mode = sampler.get_hmc_mode()
     tree_path = sampler.get_tree_path()[1] if not a.emul else "emulation"
     # ---- both gradient modes over the SAME iterations: the chain is saved (s4b_get_state), `--mode-iters` sampling iterations are

@@ -161,3 +161,55 @@ def test_rocr_environment_is_set_before_any_gpu_call():
     assert subprocess.run([sys.executable, "-c", code], cwd=ROOT).returncode == 0
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.index('os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY"') < src.index("import numpy")
+
+
+def _bench_dump(out_dir, steps):
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--burn-in", "4", "--n", "300", "--p", "10",
+           "--trees", "5", "--emul", "--no-extra-configs", "--no-cpu-baseline", "--target-n", "0", "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=dict(_clean_env(), OMP_NUM_THREADS="1"), cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs(emul_lib, tmp_path):
+    """`--dump-outputs DIR`: the last timed iteration's results as float64 .npy files, identical from run to run with the same arguments;
+    `--steps` is the number of timed iterations and `ms_per_step` their mean duration"""
+    recs = [_bench_dump(tmp_path / tag, 3) for tag in ("a", "b")]
+    for rec in recs:
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert rec["config"]["tree_updates_timed"] == 3 * 5      # 3 timed Gibbs iterations of 5 tree updates each
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bart_sigma.npy", "bart_train.npy", "bart_varcount.npy", "stan.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == names
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float64 and a.ndim == 1 and a.size > 0, name
+        assert np.array_equal(a, b), name
+    assert np.load(tmp_path / "a" / "bart_train.npy").shape == (300,)
+    assert np.load(tmp_path / "a" / "bart_varcount.npy").shape == (9,)
+    assert np.load(tmp_path / "a" / "bart_sigma.npy")[0] == recs[0]["config"]["sigma_last"][0]
+
+
+def test_bench_dump_outputs_samples_large_fits(tmp_path, monkeypatch):
+    """a fit vector above the byte budget is written as a fixed, seeded sample of its rows, with the rows' indices beside it"""
+    import importlib.util
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))     # (set by bench.py on import)
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 16)
+    n = 20000
+    train = np.arange(n, dtype=np.float64)[:, None] * 0.5
+    out = {"stan": np.ones((4, 1)), "bart": {"sigma": np.array([1.5]), "train": train, "test": np.zeros((0, 1)),
+                                             "varcount": np.arange(9, dtype=np.int32)[:, None]}}
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), out, 0, 1)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 1 << 16
+    rows, vals = np.load(tmp_path / "a" / "bart_train_rows.npy"), np.load(tmp_path / "a" / "bart_train.npy")
+    assert 0 < rows.size < n and np.all(np.diff(rows) > 0) and np.array_equal(vals, train[rows.astype(np.int64), 0])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "bart_train_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "bart_varcount.npy"), np.arange(9, dtype=np.float64))
