@@ -359,6 +359,20 @@ int S4B_FN(set_test_hook)(s4b_sampler* s, int32_t hook, int64_t value);
 /* finalizer of the externalptr — src/init.cpp:1152-1165 */
 void S4B_FN(free)(s4b_sampler* s);
 
+/* extension (no reference counterpart): SWEEP GROUP — samplers on one device whose tree sweeps are launched together, one workgroup per
+ * member, while each runs in the solo regime of the persistent path (n <= 4 096).  Samplers driven from different host threads join one
+ * group; a member's sweep then waits (bounded: s4b_sweep_group_set_timeout, default 30 s) for the other members that are inside run()
+ * at the moment and one of them launches all the sweeps at once.  Draws are identical to the ungrouped run.  A member whose sweep
+ * is not in the solo regime (more observations, another tree path) launches on its own as before and is never waited for.
+ * stats: {batched launches, member sweeps inside them, member sweeps launched on their own, launches that left a straggler behind}. */
+typedef struct s4b_sweep_group s4b_sweep_group;
+int S4B_FN(sweep_group_create)(int32_t device, int32_t max_members, s4b_sweep_group** out);
+int S4B_FN(sweep_group_join)(s4b_sweep_group* g, s4b_sampler* s);     /* refused: a sampler on another device, one already in a group, a full group */
+int S4B_FN(sweep_group_leave)(s4b_sampler* s);                        /* no-op for a sampler in no group */
+int S4B_FN(sweep_group_stats)(s4b_sweep_group* g, int64_t out[4]);
+int S4B_FN(sweep_group_set_timeout)(s4b_sweep_group* g, double seconds);
+int S4B_FN(sweep_group_free)(s4b_sweep_group* g);                     /* refused while samplers are joined */
+
 #ifdef __cplusplus
 }
 #endif

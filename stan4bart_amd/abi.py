@@ -606,6 +606,61 @@ class Sampler:
             pass
 
 
+class SweepGroup:
+    """A sweep group (include/stan4bart_amd.h ``sweep_group_*``): samplers on one device whose solo tree sweeps (n <= 4 096) go out in one
+    launch, one workgroup per member.  Members are driven from their own host threads; draws are those of the ungrouped samplers."""
+
+    STAT_NAMES = ("launches", "batched_sweeps", "unbatched_sweeps", "timeouts")
+
+    def __init__(self, lib: C.CDLL, prefix: str, device: int = 0, max_members: int = 16):
+        self._lib, self._pfx = lib, prefix
+        if getattr(lib, prefix + "sweep_group_create", None) is None:
+            raise RuntimeError("this stan4bart_amd library has no sweep groups (sweep_group_create)")
+        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+        for name, argtypes in {"sweep_group_create": [i32, i32, C.POINTER(vp)], "sweep_group_join": [vp, vp], "sweep_group_leave": [vp],
+                               "sweep_group_stats": [vp, C.POINTER(i64)], "sweep_group_set_timeout": [vp, C.c_double],
+                               "sweep_group_free": [vp]}.items():
+            fn = getattr(lib, prefix + name)
+            fn.restype, fn.argtypes = C.c_int, argtypes
+        getattr(lib, prefix + "last_error").restype = C.c_char_p
+        self._h = C.c_void_p()
+        self._check(self._f("sweep_group_create")(int(device), int(max_members), C.byref(self._h)))
+
+    def _f(self, name):
+        return getattr(self._lib, self._pfx + name)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(self._f("last_error")().decode())
+
+    def join(self, sampler: "Sampler"):
+        self._check(self._f("sweep_group_join")(self._h, sampler._h))
+
+    def leave(self, sampler: "Sampler"):
+        if getattr(sampler, "_h", None) and sampler._h.value:
+            self._check(self._f("sweep_group_leave")(sampler._h))
+
+    def set_timeout(self, seconds: float):
+        """Longest wait of a member for the others (default 30 s): after it the members present launch without the straggler."""
+        self._check(self._f("sweep_group_set_timeout")(self._h, float(seconds)))
+
+    def stats(self) -> dict:
+        out = (C.c_int64 * 4)()
+        self._check(self._f("sweep_group_stats")(self._h, out))
+        return dict(zip(self.STAT_NAMES, (int(v) for v in out)))
+
+    def free(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._check(self._f("sweep_group_free")(self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class StoredSampler:
     """``stan4bart_createStoredBARTSampler`` (reference src/init.cpp:418-446, R/stan4bart_fit.R:572-580): a sampler rebuilt
     from an exported BART state — in another process, after the fitting sampler is gone — that predicts from the kept trees."""

@@ -3,9 +3,11 @@
 // prefix emu_, test infrastructure only).  C++ exceptions never cross the boundary: they become a
 // non-zero status + message, which the R shim turns into Rf_error (reference: Rf_error at
 // src/init.cpp:319,367-382; exceptions are not caught there at all).
+#include <memory>
 #include <string>
 
 struct s4b_sampler { s4b::SamplerCore<S4B_DEV> core; template <class... A> explicit s4b_sampler(A... a) : core(a...) {} };
+struct s4b_sweep_group { std::unique_ptr<s4b::SweepGroup> g; };
 
 namespace { thread_local std::string g_last_error; }
 
@@ -25,7 +27,7 @@ int S4B_FN(create)(const s4b_bart_control* bc, const s4b_bart_data* bd, const s4
   S4B_CATCH
 }
 int S4B_FN(run)(s4b_sampler* s, int32_t num_iter, int32_t is_warmup, int32_t results_type, s4b_results* out) {
-  S4B_NEED(s, "run") S4B_TRY s->core.dev().bind(); s->core.run(num_iter, is_warmup != 0, results_type, out); S4B_CATCH
+  S4B_NEED(s, "run") S4B_TRY s->core.dev().bind(); s4b::SamplerCore<S4B_DEV>::GroupRun inRun(s->core); s->core.run(num_iter, is_warmup != 0, results_type, out); S4B_CATCH
 }
 int S4B_FN(disengage_adaptation)(s4b_sampler* s) { S4B_NEED(s, "disengageAdaptation") S4B_TRY s->core.dev().bind(); s->core.disengage_adaptation(); S4B_CATCH }
 int S4B_FN(print_initial_summary)(s4b_sampler* s) { S4B_NEED(s, "printInitialSummary") S4B_TRY s->core.dev().bind(); s->core.print_summary(); S4B_CATCH }
@@ -94,6 +96,31 @@ int S4B_FN(get_nuts_stats)(s4b_sampler* s, double out[4]) { S4B_NEED(s, "get_nut
 int S4B_FN(profile_sweep)(s4b_sampler* s, int32_t n_sweeps, double out[8]) { S4B_NEED(s, "profile_sweep") S4B_TRY s->core.dev().bind(); s->core.profile_sweep(n_sweeps, out); S4B_CATCH }
 int S4B_FN(profile_leapfrog)(s4b_sampler* s, int32_t n_evals, double out[8]) { S4B_NEED(s, "profile_leapfrog") S4B_TRY s->core.dev().bind(); s->core.profile_leapfrog(n_evals, out); S4B_CATCH }
 int S4B_FN(stream_probe)(int32_t device, int64_t n_doubles, int32_t reps, double out[4]) { S4B_TRY S4B_DEV::probe_stream(device, n_doubles, reps, out); S4B_CATCH }
-void S4B_FN(free)(s4b_sampler* s) { delete s; }
+void S4B_FN(free)(s4b_sampler* s) { if (s) { try { s->core.leave_group(); } catch (...) {} } delete s; }
+
+// sweep groups (sweep_group.hpp): SamplerCore makes the group — the device layer's batched launch or the host one — and is the members' side of it
+int S4B_FN(sweep_group_create)(int32_t device, int32_t max_members, s4b_sweep_group** out) {
+  S4B_TRY
+  if (!out) throw std::invalid_argument("sweep_group_create: NULL output pointer");
+  *out = new s4b_sweep_group{std::unique_ptr<s4b::SweepGroup>(s4b::SamplerCore<S4B_DEV>::make_group((int)device, (int)max_members))};
+  S4B_CATCH
+}
+int S4B_FN(sweep_group_join)(s4b_sweep_group* g, s4b_sampler* s) {
+  S4B_NEED(s, "sweep_group_join") S4B_TRY if (!g) throw std::invalid_argument("sweep_group_join: NULL group"); s->core.join_group(g->g.get()); S4B_CATCH
+}
+int S4B_FN(sweep_group_leave)(s4b_sampler* s) { S4B_NEED(s, "sweep_group_leave") S4B_TRY s->core.leave_group(); S4B_CATCH }
+int S4B_FN(sweep_group_stats)(s4b_sweep_group* g, int64_t out[4]) {
+  S4B_TRY if (!g || !out) throw std::invalid_argument("sweep_group_stats: NULL argument"); g->g->stats(out); S4B_CATCH
+}
+int S4B_FN(sweep_group_set_timeout)(s4b_sweep_group* g, double seconds) {
+  S4B_TRY if (!g) throw std::invalid_argument("sweep_group_set_timeout: NULL group"); g->g->set_timeout(seconds); S4B_CATCH
+}
+int S4B_FN(sweep_group_free)(s4b_sweep_group* g) {
+  S4B_TRY
+  if (!g) return 0;
+  if (g->g->members() != 0) throw std::invalid_argument("sweep_group_free: samplers are still joined (s4b_sweep_group_leave / s4b_free them first)");
+  delete g;
+  S4B_CATCH
+}
 
 }  // extern "C"

@@ -24,7 +24,7 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
-
+#include "sweep_group.hpp"
 #ifdef S4B_CONTROL_TIMING
 // (measurement build) birth proposals of candidate wave 1 in workgroup 0: time stamps inside propose()
 __device__ unsigned long long g_prop[32];
@@ -2078,6 +2078,8 @@ class DevHip {
   // may be driven from any thread (chains fitted concurrently, predict from another thread)
   void bind() { HIP_OK(hipSetDevice(device_)); }
   ~DevHip() {
+    if (group_) { group_->leave(this); group_ = nullptr; }
+    if (evReady_) (void)hipEventDestroy(evReady_);
     if (graphExec_) (void)hipGraphExecDestroy(graphExec_);
     if (graph_) (void)hipGraphDestroy(graph_);
     if (sweepStatus_) (void)hipHostFree(sweepStatus_);
@@ -2486,6 +2488,7 @@ class DevHip {
     constexpr bool dbg = false;
 #endif
     if (dbg) HIP_OK(hipEventRecord(evStart_, stream_));
+    GroupTally tally(*this, thin);
     sweep_impl(thin);
     if (dbg) {
       HIP_OK(hipEventRecord(evStop_, stream_)); sync();
@@ -2524,6 +2527,7 @@ class DevHip {
     HIP_OK(hipMemcpyAsync(cur + XC_RING_WORDS + 1, &busy, 8, hipMemcpyHostToDevice, stream_));
   }
   void sweep_persistent_launch() {
+    if (group_ && group_eligible()) { sweep_batched_launch(); return; }
     if (sweepLock_.owns_lock()) sweepLock_.unlock();      // (a previous launch whose end an exception kept us from seeing)
     sweepLock_ = std::unique_lock<std::mutex>(sweep_mutex(device_));
     for (int i = 0; i < 16; ++i) sweepStatus_[i] = 0;
@@ -2542,6 +2546,41 @@ class DevHip {
     ++launches_;
   }
   bool sweep_streams() const { return sweepStream_; }
+
+  // ---- sweep group (sweep_group.hpp, HipSweepGroup below): this sampler's solo sweeps go out in one launch with the other members' —
+  // workgroup b of k_sbatch* is member b's k_sweep* of one workgroup.  Such a launch has no roll call and no workgroup of it waits for
+  // another, so it takes no device turn: the lock of the persistent path is for launches whose workgroups must all be resident.
+  friend class HipSweepGroup;
+  SweepGroup* group_ = nullptr;
+  int64_t groupBatched_ = 0;      // sweeps of this sampler that went out in a batched launch
+  hipEvent_t evReady_ = nullptr;  // recorded on stream_ before arriving: what the batched launch waits for
+  SweepArgs batchArgs_{};         // this sweep's arguments, copied into the member's slot by the launching thread
+  static SweepGroup* group_create(int device, int maxMembers);
+  // (the solo regime of the persistent path: one workgroup, the registers' residual; busy back-off never concerns a one-workgroup launch)
+  bool group_eligible() const { return is_persistent() && sweepGrid_ == 1 && !sweepStream_; }
+  int batch_variant() const { return weighted_ ? 4 : (splitProbs_ ? (sweepFew_ ? 3 : 2) : (sweepFew_ ? 1 : 0)); }
+  void join_group(SweepGroup* g) {
+    if (group_) throw std::invalid_argument("sweep_group_join: the sampler is already in a sweep group");
+    if (g->device() != device_) throw std::invalid_argument("sweep_group_join: the sampler runs on device " + std::to_string(device_) + ", the group on device " + std::to_string(g->device()));
+    g->join(this); group_ = g;
+  }
+  void leave_group() { if (group_) { group_->leave(this); group_ = nullptr; } }
+  void sweep_batched_launch() {
+    for (int i = 0; i < 16; ++i) sweepStatus_[i] = 0;
+    sweepStatus_[0] = -1;
+    if (!evReady_) HIP_OK(hipEventCreateWithFlags(&evReady_, hipEventDisableTiming));
+    batchArgs_ = sweep_args();      // (the exchange ring a launch of its own would have had: the parity flips alike)
+    HIP_OK(hipEventRecord(evReady_, stream_));
+    GroupJob job; job.member = this; job.variant = batch_variant();
+    group_->arrive(job);            // back once the batched launch is queued and stream_ waits for its end
+    ++launches_; ++groupBatched_;
+  }
+  // the sweeps of one call of sweep / sweep_and_stan_inputs that did not go out batched are counted by the group as they end
+  struct GroupTally {
+    DevHip& d; int thin; int64_t b0;
+    GroupTally(DevHip& dd, int th) : d(dd), thin(th), b0(dd.groupBatched_) {}
+    ~GroupTally() { if (d.group_ && std::uncaught_exceptions() == 0) d.group_->count_unbatched(std::max<int64_t>(0, thin - (d.groupBatched_ - b0))); }
+  };
   SweepArgs sweep_args() {     // (the exchange ring of this launch, the one it clears for the next launch)
     unsigned long long* cur = xbuf_ + (size_t)xbufParity_ * (XC_RING_WORDS + XC_ROLL_WORDS);
     unsigned long long* nxt = xbuf_ + (size_t)(1 - xbufParity_) * (XC_RING_WORDS + XC_ROLL_WORDS);
@@ -2606,6 +2645,7 @@ class DevHip {
   // what the discarded first evaluation did to the host-side state of the fixed-point sums (scales, counters) is put back first.
   void sweep_and_stan_inputs(int thin, int mode, bool wantTrain, double* cX, double* cZ, double* s0, double* trainOut) {
     if (!is_persistent() || binary_ || thin < 1 || !persistent_now() || kModeled_) { sweep(thin); stan_inputs(mode, wantTrain, cX, cZ, s0, trainOut); return; }
+    GroupTally tally(*this, thin);
     for (int k = 0; k + 1 < thin; ++k) sweep_persistent_one();
     if (!persistent_now()) { ++sweepCount_; sweep_fused_or_two_one(); stan_inputs(mode, wantTrain, cX, cZ, s0, trainOut); return; }
     TurnGuard turn(*this);
@@ -3324,6 +3364,81 @@ class DevHip {
   int fxExp_[3] = {0, 0, 0}; int64_t fusedEvals_ = 0, fusedFallbacks_ = 0, fxLastBad_ = -2; bool fxTinyFail_ = false;
   int64_t launches_ = 0;
 };
+
+// The launch of a sweep group on the GPU: its own stream, a ring of slot buffers (pinned on the host, copied to the device on the group's
+// stream, reused once the launch that read them has ended), one batched kernel per variant present, each member's stream made to wait for
+// the end.  Queue order: the group's stream waits only on events its members recorded before arriving, and the members' streams only on the
+// event recorded here — nothing waits on an event recorded later.
+class HipSweepGroup : public SweepGroup {
+ public:
+  static constexpr int RING = 4;
+  HipSweepGroup(int device, int maxMembers) : SweepGroup(device, maxMembers) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) throw std::runtime_error("stan4bart_amd: no HIP device available — the MI355X path has no CPU fallback");
+    if (device < 0 || device >= count) throw std::runtime_error("stan4bart_amd: HIP device ordinal out of range");
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    HIP_OK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+    const size_t bytes = (size_t)maxMembers * SW_SLOT_BYTES;
+    for (int r = 0; r < RING; ++r) {
+      HIP_OK(hipHostMalloc(&host_[r], bytes, hipHostMallocDefault));
+      std::memset(host_[r], 0, bytes);
+      HIP_OK(hipMalloc(&dev_[r], bytes));
+      HIP_OK(hipEventCreateWithFlags(&used_[r], hipEventDisableTiming));
+    }
+  }
+  ~HipSweepGroup() override {
+    (void)hipSetDevice(device());
+    if (stream_) (void)hipStreamSynchronize(stream_);
+    for (int r = 0; r < RING; ++r) { if (host_[r]) (void)hipHostFree(host_[r]); if (dev_[r]) (void)hipFree(dev_[r]); if (used_[r]) (void)hipEventDestroy(used_[r]); }
+    if (done_) (void)hipEventDestroy(done_);
+    if (stream_) (void)hipStreamDestroy(stream_);
+  }
+
+ protected:
+  void launch(std::vector<GroupJob*>& jobs) override {
+    if (jobs.empty()) return;
+    if ((int)jobs.size() > max_members()) throw std::logic_error("sweep group: more jobs than members");
+    HIP_OK(hipSetDevice(device()));
+    const int r = ring_; ring_ = (ring_ + 1) % RING;
+    if (usedRec_[r]) HIP_OK(hipEventSynchronize(used_[r]));      // (the launch that read slot buffer r has ended)
+    std::stable_sort(jobs.begin(), jobs.end(), [](const GroupJob* x, const GroupJob* y) { return x->variant < y->variant; });
+    unsigned char* h = host_[r];
+    size_t lds = 0;
+    for (size_t b = 0; b < jobs.size(); ++b) {
+      const DevHip* d = static_cast<const DevHip*>(jobs[b]->member);
+      std::memcpy(h + b * SW_SLOT_BYTES, &d->a_, sizeof(BartArrays));
+      std::memcpy(h + b * SW_SLOT_BYTES + SW_SLOT_XOFF, &d->batchArgs_, sizeof(SweepArgs));
+      lds = std::max(lds, sweep_lds_bytes());
+    }
+    HIP_OK(hipMemcpyAsync(dev_[r], h, jobs.size() * SW_SLOT_BYTES, hipMemcpyHostToDevice, stream_));
+    for (GroupJob* j : jobs) HIP_OK(hipStreamWaitEvent(stream_, static_cast<DevHip*>(j->member)->evReady_, 0));
+    static void (*const kern[5])(const unsigned char*) = {k_sbatch, k_sbatch_few, k_sbatch_sp, k_sbatch_few_sp, k_sbatch_w};
+    for (size_t b0 = 0; b0 < jobs.size();) {
+      const int v = jobs[b0]->variant;
+      size_t b1 = b0;
+      while (b1 < jobs.size() && jobs[b1]->variant == v) ++b1;
+      if (v < 0 || v > 4) throw std::logic_error("sweep group: unknown variant");
+      if (ldsSet_[v] < lds) { HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern[v]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); ldsSet_[v] = lds; }
+      hipLaunchKernelGGL(kern[v], dim3((unsigned)(b1 - b0)), dim3(FBLOCK), lds, stream_, (const unsigned char*)(dev_[r] + b0 * SW_SLOT_BYTES));
+      HIP_OK(hipGetLastError());
+      b0 = b1;
+    }
+    HIP_OK(hipEventRecord(done_, stream_));
+    HIP_OK(hipEventRecord(used_[r], stream_)); usedRec_[r] = true;
+    for (GroupJob* j : jobs) HIP_OK(hipStreamWaitEvent(static_cast<DevHip*>(j->member)->stream_, done_, 0));
+  }
+
+ private:
+  hipStream_t stream_ = nullptr;
+  hipEvent_t done_ = nullptr, used_[RING] = {};
+  unsigned char* host_[RING] = {};
+  unsigned char* dev_[RING] = {};
+  bool usedRec_[RING] = {};
+  size_t ldsSet_[5] = {0, 0, 0, 0, 0};
+  int ring_ = 0;
+};
+inline SweepGroup* DevHip::group_create(int device, int maxMembers) { return new HipSweepGroup(device, maxMembers); }
 
 #endif   // S4B_SWEEP_TU
 }  // namespace s4b

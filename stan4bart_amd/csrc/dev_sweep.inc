@@ -42,7 +42,7 @@
 #if defined(S4B_SWEEP_TIMING) || defined(S4B_SWEEP_WGT) || defined(S4B_SWEEP_WGD)
 // per-workgroup stamps of the exchange (`-DS4B_SWEEP_WGT` alone: nothing else is timed, every workgroup carries the same four atomics per step)
 #define S4B_SWEEP_WG 1
-#define SW_W(i) do { if (lane == 0 && t > 0 && t < T && (int)blockIdx.x < 256) atomicAdd(&g_wg[blockIdx.x * 16 + (i)], (unsigned long long)wall_clock64() - (unsigned long long)F.t0[t & 3]); } while (0)
+#define SW_W(i) do { if (lane == 0 && t > 0 && t < T && (int)SW_BX < 256) atomicAdd(&g_wg[SW_BX * 16 + (i)], (unsigned long long)wall_clock64() - (unsigned long long)F.t0[t & 3]); } while (0)
 #ifdef S4B_SWEEP_TU
 __device__ unsigned long long g_pubMax[8], g_pubMin[8];     // wall clock of the last / first speculative publish of step t (slot t & 7)
 // per workgroup: [0] sum of (speculative publish - totals seen) [1] steps [2] sum of the wall clock when the totals were seen [3] steps
@@ -61,7 +61,7 @@ __device__ __attribute__((noinline)) void sw_dur_add(int idx, unsigned long long
 //  values, 2 decider past its wait for the pass waves, 3 verdict out, 4 decider's step ends, 5 wave 1 starts drawing the ahead image, 6 wave 1 has drawn it, 7 proposal settled (paGo))
 __device__ __attribute__((noinline)) void sw_abs_add(int idx, long long v) { atomicAdd(&g_wd[idx], (unsigned long long)v); atomicAdd(&g_wd[idx + 16], 1ull); }
 #ifdef S4B_SWEEP_WGD
-#define SW_ABS(i) do { if (lane == 0 && t > 1 && t + 1 < T && (int)blockIdx.x < 256) sw_abs_add((int)blockIdx.x * 64 + 32 + (i), wall_clock64() - F.t0[t & 3]); } while (0)
+#define SW_ABS(i) do { if (lane == 0 && t > 1 && t + 1 < T && (int)SW_BX < 256) sw_abs_add((int)SW_BX * 64 + 32 + (i), wall_clock64() - F.t0[t & 3]); } while (0)
 #endif
 void sweep_wd_fetch(unsigned long long* out) {   // (reads and clears)
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wd), sizeof(g_wd));
@@ -87,10 +87,10 @@ void sweep_wd_fetch(unsigned long long* out);
 // durations of pass wave 5's phases (linear statistics), g_wd[workgroup][i] sums and [8 + i] counts: [0] end of the previous step -> leaf ids of the next tree requested,
 // staging, [1] wait for the image drawn ahead, [2] routing under it, [3] wait for wave 3's leaf values, [4] the ahead pass, [5] wait for the verdict + fold, [6] the step done the old way
 #define SW_D0() tDur = wall_clock64()
-#define SW_D(i) do { const long long nw_ = wall_clock64(); if (pw == 1 && lane == 0 && t > 1 && t + 1 < T && (int)blockIdx.x < 256 && tDur != 0) sw_dur_add((int)blockIdx.x * 64 + (i), (unsigned long long)(nw_ - tDur)); tDur = nw_; } while (0)
+#define SW_D(i) do { const long long nw_ = wall_clock64(); if (pw == 1 && lane == 0 && t > 1 && t + 1 < T && (int)SW_BX < 256 && tDur != 0) sw_dur_add((int)SW_BX * 64 + (i), (unsigned long long)(nw_ - tDur)); tDur = nw_; } while (0)
 #endif
 #ifdef S4B_SWEEP_TIMING
-#define SW_TIMED_WG (gridDim.x == 1 ? 0 : 100)     // (the instrumented workgroup: 100; the only one of a one-workgroup launch)
+#define SW_TIMED_WG (SW_GX == 1 ? 0 : 100)     // (the instrumented workgroup: 100; the only one of a one-workgroup launch)
 // phase timers (100 MHz clock) of workgroup 100, accumulated in LDS (F.tacc: no global traffic inside the steps) and flushed to g_sw
 // when the launch ends; `make sweeptiming`, printed by s4b_profile_sweep (dev_hip.hip profile_sweep_persistent).  Slots:
 //   relative to the moment the wave that takes the stamp finished its previous step (SW_T):
@@ -120,14 +120,14 @@ void sweep_decide_fetch(unsigned long long* out) {   // (reads and clears)
 void sweep_timing_fetch(unsigned long long* out);
 void sweep_decide_fetch(unsigned long long* out);
 #endif
-#define SW_T(i) do { if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 0 && t < T) atomicAdd(&F.tacc[i], (unsigned long long)(wall_clock64() - tStep)); } while (0)
+#define SW_T(i) do { if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T) atomicAdd(&F.tacc[i], (unsigned long long)(wall_clock64() - tStep)); } while (0)
 #define SW_MARK() tStep = wall_clock64()
-#define SW_AP(i) do { if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 1 && t < T) atomicAdd(&F.tacc[i], (unsigned long long)(wall_clock64() - F.t0[(t - 1) & 3])); } while (0)
+#define SW_AP(i) do { if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 1 && t < T) atomicAdd(&F.tacc[i], (unsigned long long)(wall_clock64() - F.t0[(t - 1) & 3])); } while (0)
 // absolute timeline of a step: SW_A(i) adds (now - the moment the totals of THIS step were complete in this workgroup), signed
-#define SW_A(i) do { if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 0 && t < T) atomicAdd(&F.tacc[i], (unsigned long long)(wall_clock64() - F.t0[t & 3])); } while (0)
+#define SW_A(i) do { if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T) atomicAdd(&F.tacc[i], (unsigned long long)(wall_clock64() - F.t0[t & 3])); } while (0)
 // (the speculative path: straight to g_sw — [88] steps borne out [89] steps that speculated; timeline like SW_A: [90] wave 5 starts the speculative statistics
 //  [91] wave 4 has published them [92] wave 5 past foldReady [93] wave 5 through with the step [94] wave 3 past paGo (its step ends) [95] decider's step ends)
-#define SW_G(i) do { if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 0 && t < T) atomicAdd(&g_sw[i], (unsigned long long)(wall_clock64() - F.t0[t & 3])); } while (0)
+#define SW_G(i) do { if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T) atomicAdd(&g_sw[i], (unsigned long long)(wall_clock64() - F.t0[t & 3])); } while (0)
 #else
 #define SW_G(i)
 #define SW_T(i)
@@ -332,11 +332,11 @@ __device__ __forceinline__ void pass_barrier(PassBar& b) {
 // block of a step needs them: otherwise every field the loop touches is loaded once before the loop and stays live across it —
 // hundreds of scalar registers spilled into vector registers, and those into scratch memory.
 #define SW_KERNARGS()                                                                                                        \
-  auto kp_ = (const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr();                  \
+  auto kp_ = (const __attribute__((address_space(4))) unsigned char*)__builtin_amdgcn_kernarg_segment_ptr(); SW_SLOT_OF(kp_);  \
   asm volatile("" : "+s"(kp_));                                                                                              \
   const BartArrays& a = *(const BartArrays*)kp_;                                                                             \
   const SweepArgs& x = *(const SweepArgs*)(kp_ + (sizeof(BartArrays) + 7) / 8 * 8); (void)x; (void)a
-
+#include "sweep_batch.inc"
 #ifndef S4B_SWEEP_TU
 __global__ __launch_bounds__(FBLOCK) void k_sweep(BartArrays aKern, SweepArgs xKern);
 __global__ __launch_bounds__(FBLOCK) void k_sweep_stream(BartArrays aKern, SweepArgs xKern);
@@ -500,7 +500,7 @@ __device__ __forceinline__ int sweep_fresh_lane() {
 // w (r + mu), and a third statistic per bin, the sum of the weights, travels as bin nbAll + k of the same exchange — sum in the sum field, count 0 —: the
 // step then exchanges 2 nbAll "bins", which is why such a launch takes trees of at most 32 bins.  Both are published times wScale, a power of two that brings
 // the largest weight into (0.5, 1]: the fixed-point words hold sums of O(1) terms; the gathering side multiplies by its inverse.  Exact either way.)
-template <int NB, bool SKIP, bool LIN, bool WT = false>
+template <int NB, bool SKIP, bool LIN, bool WT = false, bool BATCH = false>
 __device__ __forceinline__ bool sweep_stats(const BartArrays& a, const SweepLds& L, PassBar& bar, const double (&r)[SW_PF][4], const lfq_t (&lf)[SW_PF], const NodeS* __restrict__ Ssel,
                                             const unsigned (&bb)[SW_PF], int64_t q0, int64_t stride, int64_t nQuads, int base, unsigned long long* xcur, double* part_,
                                             bool alsoPart, int pw, int lane, long long tRef = 0,
@@ -509,7 +509,7 @@ __device__ __forceinline__ bool sweep_stats(const BartArrays& a, const SweepLds&
                                             const double* __restrict__ wq = nullptr, int nbAll = 0, double wScale = 1.0) {
   static_assert(!WT || (S4B_WAVERED && !LIN), "the weighted statistics exist for the per-wave reduction of the default build only");
 #ifdef S4B_SWEEP_TIMING
-#define SWS_T(i, cond) do { if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && tRef != 0 && (cond)) atomicAdd(&bar.tacc[i], (unsigned long long)(wall_clock64() - tRef)); } while (0)
+#define SWS_T(i, cond) do { if ((int)SW_BX == SW_TIMED_WG && lane == 0 && tRef != 0 && (cond)) atomicAdd(&bar.tacc[i], (unsigned long long)(wall_clock64() - tRef)); } while (0)
 #else
 #define SWS_T(i, cond)
 #endif
@@ -633,9 +633,9 @@ __device__ __forceinline__ bool sweep_stats(const BartArrays& a, const SweepLds&
     if (lane < NB) {
       if (alsoPart) {
         const size_t kind = (size_t)a.binCap * a.gridF;
-        part_[(size_t)(base + k) * a.gridF + blockIdx.x] = sm;
-        part_[kind + (size_t)(base + k) * a.gridF + blockIdx.x] = (double)c;
-        if (WT) part_[2 * kind + (size_t)(base + k) * a.gridF + blockIdx.x] = wsum;
+        part_[(size_t)(base + k) * a.gridF + SW_BX] = sm;
+        part_[kind + (size_t)(base + k) * a.gridF + SW_BX] = (double)c;
+        if (WT) part_[2 * kind + (size_t)(base + k) * a.gridF + SW_BX] = wsum;
       }
       // (WT: the instantiation may carry more bins than the step has left — NB = 3 for two —: without weights the surplus lands in slots nobody reads; here the slots
       // behind the last bin ARE the sums of the weights)
@@ -670,8 +670,8 @@ __device__ __forceinline__ bool sweep_stats(const BartArrays& a, const SweepLds&
     else if (part == 0 && k < NB) {
       if (alsoPart) {
         const size_t kind = (size_t)a.binCap * a.gridF;
-        part_[(size_t)(base + k) * a.gridF + blockIdx.x] = sm;
-        part_[kind + (size_t)(base + k) * a.gridF + blockIdx.x] = (double)c;
+        part_[(size_t)(base + k) * a.gridF + SW_BX] = sm;
+        part_[kind + (size_t)(base + k) * a.gridF + SW_BX] = (double)c;
       }
       if (bar.solo) { bar.totS[base + k] = sm; bar.totC[base + k] = (double)c; }
       else xc_publish(xcur, base + k, sm, c, a.errFlag);
@@ -770,7 +770,7 @@ __device__ __forceinline__ bool sweep_stats_pre_n(int n, const BartArrays& a, co
   else if (n <= 5) return sweep_stats_pre<5, SKIP>(a, L, bar, r, lf, Ssel, bitsQ, xcur, pw, lane, foldLf, foldA, jMax, cntSlot);
   return sweep_stats_pre<8, SKIP>(a, L, bar, r, lf, Ssel, bitsQ, xcur, pw, lane, foldLf, foldA, jMax, cntSlot);
 }
-template <int NB, bool SKIP, bool LIN = false, bool WT = false>
+template <int NB, bool SKIP, bool LIN = false, bool WT = false, bool BATCH = false>
 __device__ __forceinline__ bool sweep_stats_n(int n, const BartArrays& a, const SweepLds& L, PassBar& bar, const double (&r)[SW_PF][4], const lfq_t (&lf)[SW_PF], const NodeS* __restrict__ Ssel,
                                               const unsigned (&bb)[SW_PF], int64_t q0, int64_t stride, int64_t nQuads, int base, unsigned long long* xcur, double* part,
                                               bool alsoPart, int pw, int lane, long long tRef = 0,
@@ -782,11 +782,11 @@ __device__ __forceinline__ bool sweep_stats_n(int n, const BartArrays& a, const 
   // usual proposals — a tree of 2-3 leaves + a birth, 4-6 leaves + a change — at a third more work than the exact count at most
   // (a 6-bin instantiation, round 5, stationary chain with 5.0 bins per step on average: 18 spilled registers instead of 14, sweep 2.21 instead of 2.165 ms);
   // more than 8 bins take several passes)
-  if (n <= 3) return sweep_stats<3, SKIP, LIN, WT>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
-  else if (n <= 4) return sweep_stats<4, SKIP, LIN, WT>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
-  else if (n <= 5) return sweep_stats<5, SKIP, LIN, WT>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
-  else if (n <= 8) return sweep_stats<8, SKIP, LIN, WT>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
-  else return sweep_stats<8, SKIP, LIN, WT>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  if (n <= 3) return sweep_stats<3, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  else if (n <= 4) return sweep_stats<4, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  else if (n <= 5) return sweep_stats<5, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  else if (n <= 8) return sweep_stats<8, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  else return sweep_stats<8, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
 }
 
 
@@ -1037,8 +1037,8 @@ __device__ __forceinline__ void stream_pass_n(int nbThis, const BartArrays& a, c
   else stream_pass<8, APPLY, STATS>(a, L, bar, st, tS, tA, q0, stride, nQuads, xcur, part, alsoPart, pw, lane);
 }
 
-template <bool STREAM, bool FEW, bool SPL = false, bool WT = false>
-__device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
+template <bool STREAM, bool FEW, bool SPL = false, bool WT = false, bool BATCH = false, class AK = BartArrays, class XK = SweepArgs>
+__device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH: AK / XK are placeholders, the arguments come from the member's slot)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ ControlShared S;
   __shared__ SweepShared F;
@@ -1046,7 +1046,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
   __shared__ double spTab[SPL ? SP_TAB : 1];      // (cgm(split.probs): WaveModelT<true>, dev_hip.hip)
   __shared__ __attribute__((aligned(16))) double wLds[WT ? SW_PT * SW_PF * 4 : 2];      // (observation weights of the workgroup's observations: sweep_stats<.., WT>)
   constexpr int NBX = WT ? 2 : 1;      // "bins" a step exchanges per bin of its statistics (the sums of the weights travel as bins of their own)
-  static_assert(!(WT && STREAM), "no weighted streaming sweep");
+  static_assert(!(WT && STREAM), "no weighted streaming sweep"); static_assert(!(BATCH && STREAM), "the streaming sweep is never solo");
   (void)xKern; (void)spTab; (void)wLds;
   // waits: k_sweep's steps are ~10 us of dependent hand-overs — its control waves poll every 64 cycles at raised priority; a step of the
   // streaming variant is dominated by the pass (tens of us), during which every control wave of the workgroup only waits: there they
@@ -1055,14 +1055,14 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   constexpr int MTW = (int)(sizeof(MTState) / 4), MTJ = (MTW + 63) / 64;
-  const int T = aKern.T;
+  int T_ = 0; if constexpr (BATCH) { SW_KERNARGS(); T_ = a.T; } else T_ = aKern.T; const int T = T_;      // (BATCH: T from the member's slot)
   // SOLO (gridDim.x == 1, at most SW_PT * SW_PF quads = 4096 observations): one workgroup holds every observation AND the control
   // duties; the bin totals never leave the chip — wave 4's reduction IS the total, no exchange words, no polling (a tree update then
   // costs what the decision and the pass cost, not a trip through memory)
-  const bool solo = gridDim.x == 1;
-  const int NP = solo ? 1 : (int)gridDim.x - 1;   // workgroups with observations
-  const bool ctl = solo || (int)blockIdx.x == NP; // writes the decided trees / the trace to the main arrays
-  const bool hasObs = solo || (int)blockIdx.x < NP;
+  const bool solo = SW_GX == 1;
+  const int NP = solo ? 1 : (int)SW_GX - 1;   // workgroups with observations
+  const bool ctl = solo || (int)SW_BX == NP; // writes the decided trees / the trace to the main arrays
+  const bool hasObs = solo || (int)SW_BX < NP;
   const SweepLds L = carve_sweep(smem);
   {
     SW_KERNARGS();
@@ -1087,7 +1087,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
       if (threadIdx.x == 0) {
         const unsigned long long k = __hip_atomic_fetch_add(roll, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         unsigned long long w = 0ull;
-        if (k + 1 == (unsigned long long)gridDim.x) { unsigned long long z = 0ull; __hip_atomic_compare_exchange_strong(roll + 1, &z, SW_ROLL_GO, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+        if (k + 1 == (unsigned long long)SW_GX) { unsigned long long z = 0ull; __hip_atomic_compare_exchange_strong(roll + 1, &z, SW_ROLL_GO, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
         const long long t0 = wall_clock64();
         while ((w = __hip_atomic_load(roll + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0ull) {
           __builtin_amdgcn_s_sleep(4);
@@ -1147,7 +1147,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
         const int64_t nQuadsW = (a.n + 3) >> 2;
 #pragma unroll
         for (int j = 0; j < SW_PF; ++j) {
-          const int64_t qd = (int64_t)blockIdx.x * SW_PT + ptW + (int64_t)j * NP * SW_PT;
+          const int64_t qd = (int64_t)SW_BX * SW_PT + ptW + (int64_t)j * NP * SW_PT;
 #pragma unroll
           for (int e = 0; e < 4; ++e) { const int64_t i = (qd << 2) + e; wLds[((size_t)j * SW_PT + ptW) * 4 + e] = (hasObs && qd < nQuadsW && i < a.n) ? a.wts[i] : 0.0; }
         }
@@ -1326,7 +1326,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
           earlyDone = true;
           SW_T(10); SW_T(11); SW_A(43);
 #ifdef S4B_SWEEP_TIMING
-          if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 0 && t < T) atomicAdd(&F.tacc[35], 1ull);
+          if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T) atomicAdd(&F.tacc[35], 1ull);
 #endif
           // wave 3's values ARE the leaf values (same statistics, same stream positions, same arithmetic): this wave takes them over instead
           // of drawing them again — the generator moves past their uniforms (no block renewal among them: wave 3's `valid`), node n's lane
@@ -1545,7 +1545,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
 #endif
         const int perr = propose(curN, hwmP, m, &rng, &prN, tbN, caN);
 #ifdef S4B_SWEEP_TIMING
-        if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && wv == 1) { atomicAdd(&g_sw[24 + (prN.type & 3)], (unsigned long long)(wall_clock64() - tPr0)); atomicAdd(&g_sw[36 + (prN.type & 3)], 1ull);
+        if ((int)SW_BX == SW_TIMED_WG && lane == 0 && wv == 1) { atomicAdd(&g_sw[24 + (prN.type & 3)], (unsigned long long)(wall_clock64() - tPr0)); atomicAdd(&g_sw[36 + (prN.type & 3)], 1ull);
                                                              if (prN.status != 1) atomicAdd(&g_sw[62], 1ull); if (aheadDraw) atomicAdd(&g_sw[69], 1ull); else atomicAdd(&g_sw[64], 1ull); }
 #endif
         rng.close();
@@ -1715,7 +1715,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
 #ifdef S4B_SWEEP_WG
         if (lane == 0) {
           const unsigned long long nw = (unsigned long long)wall_clock64();
-          const int b = (int)blockIdx.x;
+          const int b = (int)SW_BX;
           F.t0[t & 3] = (long long)nw;
           if (t > 0 && t < T && b < 256) { atomicAdd(&g_wg[b * 16 + 2], nw); atomicAdd(&g_wg[b * 16 + 3], 1ull); }
           if (t > 1 && t < T && b < 256) {
@@ -1777,7 +1777,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
 #endif
             if (prevOk && S4B_LINEAR != 2) spin_counter(&F.preDoneA, t, &F.abort); else spin_counter(&F.preDoneB, t, &F.abort);
 #ifdef S4B_SWEEP_WGD
-            if (lane == 0 && t > 1 && t + 1 < T && (int)blockIdx.x < 256) sw_dur_add((int)blockIdx.x * 64 + 7, (unsigned long long)(wall_clock64() - tW0));
+            if (lane == 0 && t > 1 && t + 1 < T && (int)SW_BX < 256) sw_dur_add((int)SW_BX * 64 + 7, (unsigned long long)(wall_clock64() - tW0));
 #endif
             const int pnb = S4B_UNI(F.preNb[t & 1]), pseq = S4B_UNI(F.preSeq[t & 1]);
             if (pnb == specNbPre && pseq == seqImg) nbLin = pnb;
@@ -1817,9 +1817,9 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
               }
               if (lane < specNb) xc_publish(ring, lane, sL, (int)cL, a.errFlag);
 #ifdef S4B_SWEEP_WG
-              if (lane == 0 && t > 0 && t < T && (int)blockIdx.x < 256) {
+              if (lane == 0 && t > 0 && t < T && (int)SW_BX < 256) {
                 const unsigned long long nw = (unsigned long long)wall_clock64();
-                atomicAdd(&g_wg[blockIdx.x * 16], nw - (unsigned long long)F.t0[t & 3]); atomicAdd(&g_wg[blockIdx.x * 16 + 1], 1ull);
+                atomicAdd(&g_wg[SW_BX * 16], nw - (unsigned long long)F.t0[t & 3]); atomicAdd(&g_wg[SW_BX * 16 + 1], 1ull);
                 atomicMax(&g_pubMax[t & 7], nw); atomicMin(&g_pubMin[t & 7], nw);
               }
 #endif
@@ -1842,7 +1842,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
         // re-arm: the exchange buffers of step t-2 — the ones step t+2 publishes into — are dead: whoever has published in step t-1, and
         // everybody has (the totals of this step are complete), had gathered them before.  (Completion: see the top of the next step.)
         if (!ctl && !solo) {
-          for (int c = (int)blockIdx.x; c < 2 * XC_COPIES; c += NP) {   // (pass workgroup b re-arms copies b, b + NP, ... of the two rings)
+          for (int c = (int)SW_BX; c < 2 * XC_COPIES; c += NP) {   // (pass workgroup b re-arms copies b, b + NP, ... of the two rings)
             unsigned long long* z = x.xbuf + (size_t)((c >= XC_COPIES ? XC_RING : 0) + ((t + 2) & (XC_RING - 1))) * XC_BUF_WORDS + (size_t)(c & (XC_COPIES - 1)) * XC_WORDS;
             __hip_atomic_store(z + lane, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(z + 64 + lane, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1874,7 +1874,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
     // ====================================================================================== waves 4-7: the pass waves
     const int pw = wv - 4, pt = pw * 64 + lane;       // pass wave / pass thread of the workgroup
     const int64_t stride = (int64_t)NP * SW_PT;
-    const int64_t q0 = (int64_t)blockIdx.x * SW_PT + pt;
+    const int64_t q0 = (int64_t)SW_BX * SW_PT + pt;
     PassBar bar; bar.ctr = &F.bar; bar.abortFlag = &F.abort; bar.epoch = 0; bar.tacc = F.tacc; bar.totS = F.totS; bar.totC = F.totC; bar.solo = solo; bar.arr = &F.statArr;
     if constexpr (STREAM) {
       // ---- streaming pass (see stream_pass): per step, wait for the verdict, the leaf values and the settled proposal, then one pass over
@@ -1965,7 +1965,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
       // quads the threads of this workgroup own at most (thread 0 owns the most): a launch over few observations skips the unrolled work of the others
       int jMax = 0;
 #pragma unroll
-      for (int j = 0; j < SW_PF; ++j) jMax += ((int64_t)blockIdx.x * SW_PT + (int64_t)j * stride < nQuads) ? 1 : 0;
+      for (int j = 0; j < SW_PF; ++j) jMax += ((int64_t)SW_BX * SW_PT + (int64_t)j * stride < nQuads) ? 1 : 0;
       jMax = __builtin_amdgcn_readfirstlane(jMax);
       // ---- leaf ids of the tree AFTER next: requested now, used from the next step on (lfNext — the tree whose statistics are gathered ahead during this step — was
       // requested a step ago)
@@ -2142,7 +2142,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
               for (int base = 0; base < nb; base += 8) {   // (8 bins per pass: sixteen accumulator pairs would not fit the registers beside the 16 observations)
                 if (base > 0) pass_barrier(bar);     // the reduction slots are free again
                 const int nbThis = nb - base < 8 ? nb - base : 8;
-                lastW = sweep_stats_n<8, FEW, false>(nbThis, a, L, bar, O.r, lfCur, Ssel, bb, q0p, stride, nQuads, base, xCur, partOut, bail, pw, lnP, 0, nullptr, nullptr, nullptr, nullptr, jMax);
+                lastW = sweep_stats_n<8, FEW, false, false, BATCH>(nbThis, a, L, bar, O.r, lfCur, Ssel, bb, q0p, stride, nQuads, base, xCur, partOut, bail, pw, lnP, 0, nullptr, nullptr, nullptr, nullptr, jMax);
               }
             }
             // (the wave that published — the last of the four to arrive at the reduction — says so)
@@ -2211,7 +2211,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
         if (run && hasObs) {
           __builtin_amdgcn_s_setprio(S4B_PRIO_SPEC);
           if (pw == 1 && phase == 0) { SW_G(90); SW_W(9); }
-          sweep_stats_n<8, FEW, true>(nbNext, a, L, bar, O.r, lfNext, L.S + (1 + sw_slot(t + 1, 0)) * SW_NC, bbNext, q0p, stride, nQuads, 0, nullptr, nullptr, false, pw, lnP, 0,
+          sweep_stats_n<8, FEW, true, false, BATCH>(nbNext, a, L, bar, O.r, lfNext, L.S + (1 + sw_slot(t + 1, 0)) * SW_NC, bbNext, q0p, stride, nQuads, 0, nullptr, nullptr, false, pw, lnP, 0,
                                       &O.lfPrev, nullptr, nullptr, nullptr, jMax, &lfCur, L.ctab + (size_t)par1 * SW_CT_WORDS, L.preS + par1 * SW_PW * 8, foldD);
           __builtin_amdgcn_s_setprio(0);
           ranAhead = true;
@@ -2298,7 +2298,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
       // quads the threads of this workgroup own at most (thread 0 owns the most): a launch over few observations skips the unrolled work of the others
       int jMax = 0;
 #pragma unroll
-      for (int j = 0; j < SW_PF; ++j) jMax += ((int64_t)blockIdx.x * SW_PT + (int64_t)j * stride < nQuads) ? 1 : 0;
+      for (int j = 0; j < SW_PF; ++j) jMax += ((int64_t)SW_BX * SW_PT + (int64_t)j * stride < nQuads) ? 1 : 0;
       jMax = __builtin_amdgcn_readfirstlane(jMax);
       // ---- the statistics half, as far as it does not depend on the pending decision: leaf ids of the observations in tree tn,
       // their A bins and leaf values, and their B bins under image 0 of the tree's proposal
@@ -2363,13 +2363,13 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
           if (pw == 0) SW_T(3);
           if (pw == 1) {  SW_AP(44); }
 #ifdef S4B_SWEEP_TIMING
-          if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 0 && t < T && pw == 1 && __hip_atomic_load(&F.foldReady, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= t) {
+          if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T && pw == 1 && __hip_atomic_load(&F.foldReady, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= t) {
             atomicAdd(&F.tacc[55], 1ull); atomicAdd(&F.tacc[56], (unsigned long long)(wall_clock64() - F.tFold));
             atomicAdd(&F.tacc[57], (unsigned long long)(wall_clock64() - tImgSeen)); atomicAdd(&F.tacc[58], (unsigned long long)(tImgSeen - F.t0[t & 3]));
             atomicAdd(&F.tacc[59], (unsigned long long)(F.bothStep == t ? 1 : 0));
             atomicAdd(&F.tacc[28], (unsigned long long)(tImgSeen - tImgWait));
             atomicAdd(&F.tacc[20 + (cand_lds(L.img, tn, 0).head->pr.type & 3)], 1ull); }
-          else if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 0 && t < T && pw == 1) {
+          else if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T && pw == 1) {
             atomicAdd(&F.tacc[60], (unsigned long long)(wall_clock64() - tImgSeen)); atomicAdd(&F.tacc[61], (unsigned long long)(tImgSeen - F.t0[(t - 1) & 3])); }
 #endif
         }
@@ -2411,25 +2411,25 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
           const bool lastS = preBits
               ? sweep_stats_pre_n<FEW>(nbSpec, a, L, bar, O.r, lf, L.S + (1 + sw_slot(tn, 0)) * SW_NC, bitsQ, x.xbuf + (size_t)(t & (XC_RING - 1)) * XC_BUF_WORDS, pw, lane, O.lfPrev, At,
                                        jMax, L.redN + 64 + (t & 1) * 32)
-              : sweep_stats_n<8, FEW>(nbSpec, a, L, bar, O.r, lf, L.S + (1 + sw_slot(tn, 0)) * SW_NC, bbI[0], q0, stride, nQuads, 0,
+              : sweep_stats_n<8, FEW, false, false, BATCH>(nbSpec, a, L, bar, O.r, lf, L.S + (1 + sw_slot(tn, 0)) * SW_NC, bbI[0], q0, stride, nQuads, 0,
                            x.xbuf + (size_t)(t & (XC_RING - 1)) * XC_BUF_WORDS, nullptr, false, pw, lane, 0, &O.lfPrev, At, nullptr, nullptr, jMax);
 #else
-          const bool lastS = sweep_stats_n<8, FEW, false, WT>(nbSpec, a, L, bar, O.r, lf, L.S + (1 + sw_slot(tn, 0)) * SW_NC, bbI[0], q0, stride, nQuads, 0,
+          const bool lastS = sweep_stats_n<8, FEW, false, WT, BATCH>(nbSpec, a, L, bar, O.r, lf, L.S + (1 + sw_slot(tn, 0)) * SW_NC, bbI[0], q0, stride, nQuads, 0,
                            x.xbuf + (size_t)(t & (XC_RING - 1)) * XC_BUF_WORDS, nullptr, false, pw, lane, 0, &O.lfPrev, At, solo ? &specS : nullptr, solo ? &specC : nullptr, jMax,
                            nullptr, nullptr, nullptr, nullptr, wLds + (size_t)pt * 4, nbSpec, x.wScale);
 #endif
           if (lastS) { if (lane == 0 && !solo) __hip_atomic_store(&F.published, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); SW_A(50); SW_G(91);
 #ifdef S4B_SWEEP_WG
-            if (lane == 0 && t > 0 && t < T && (int)blockIdx.x < 256) {
+            if (lane == 0 && t > 0 && t < T && (int)SW_BX < 256) {
               const unsigned long long nw = (unsigned long long)wall_clock64();
-              atomicAdd(&g_wg[blockIdx.x * 16], nw - (unsigned long long)F.t0[t & 3]); atomicAdd(&g_wg[blockIdx.x * 16 + 1], 1ull);
+              atomicAdd(&g_wg[SW_BX * 16], nw - (unsigned long long)F.t0[t & 3]); atomicAdd(&g_wg[SW_BX * 16 + 1], 1ull);
               atomicMax(&g_pubMax[t & 7], nw); atomicMin(&g_pubMin[t & 7], nw);
             }
 #endif
           }
           __builtin_amdgcn_s_setprio(0);
 #ifdef S4B_SWEEP_TIMING
-          if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && pw == 0 && t < T) atomicAdd(&g_sw[89], 1ull);
+          if ((int)SW_BX == SW_TIMED_WG && lane == 0 && pw == 0 && t < T) atomicAdd(&g_sw[89], 1ull);
 #endif
         }
       }
@@ -2441,7 +2441,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
       if (doDecide) {
         spin_counter(&F.foldReady, t, &F.abort);
 #ifdef S4B_SWEEP_TIMING
-        if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 0 && t < T && pw <= 1) atomicAdd(&F.tacc[53 + pw], (unsigned long long)(wall_clock64() - F.tFold));
+        if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T && pw <= 1) atomicAdd(&F.tacc[53 + pw], (unsigned long long)(wall_clock64() - F.tFold));
 #endif
         if (pw == 1) SW_A(45);
         bothHalves = __builtin_amdgcn_readfirstlane(F.bothStep) == t;
@@ -2470,7 +2470,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
               for (int j = 0; j < SW_PF; ++j) { O.lfPrev[j] = lf[j]; O.bbPrev[j] = bbI[0][j]; }
               if (pw == 0) { SW_T(6);
 #ifdef S4B_SWEEP_TIMING
-                if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 0 && t < T) { atomicAdd(&F.tacc[0], 1ull); atomicAdd(&F.tacc[7], (unsigned long long)nbSpec); atomicAdd(&g_sw[72 + (nbSpec < 15 ? nbSpec : 15)], 1ull); atomicAdd(&g_sw[88], 1ull); }
+                if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T) { atomicAdd(&F.tacc[0], 1ull); atomicAdd(&F.tacc[7], (unsigned long long)nbSpec); atomicAdd(&g_sw[72 + (nbSpec < 15 ? nbSpec : 15)], 1ull); atomicAdd(&g_sw[88], 1ull); }
 #endif
               }
             }
@@ -2541,7 +2541,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
           for (int j = 0; j < SW_PF; ++j) bb[j] = bbI[0][j];
         } else if (doPropose) {
 #ifdef S4B_SWEEP_TIMING
-          if ((int)blockIdx.x == SW_TIMED_WG && pw == 0 && lane == 0 && t > 0) atomicAdd(&F.tacc[8], 1ull);
+          if ((int)SW_BX == SW_TIMED_WG && pw == 0 && lane == 0 && t > 0) atomicAdd(&F.tacc[8], 1ull);
 #endif
           const NodeS* Sx = L.S + sset * SW_NC;
           {
@@ -2581,7 +2581,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
           for (int base = 0; base < nb; base += 8) {   // (8 bins per pass: sixteen accumulator pairs would not fit the registers beside the 16 observations)
             if (base > 0) pass_barrier(bar);     // the reduction slots are free again
             const int nbThis = nb - base < 8 ? nb - base : 8;
-            lastW = sweep_stats_n<8, FEW, false, WT>(nbThis, a, L, bar, O.r, lf, Ssel, bb, q0, stride, nQuads, base, xCur, partOut, bail, pw, lane,
+            lastW = sweep_stats_n<8, FEW, false, WT, BATCH>(nbThis, a, L, bar, O.r, lf, Ssel, bb, q0, stride, nQuads, base, xCur, partOut, bail, pw, lane,
 #ifdef S4B_SWEEP_TIMING
                              (t > 0 && t < T) ? tStep : 0,
 #else
@@ -2598,7 +2598,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
         for (int j = 0; j < SW_PF; ++j) { O.lfPrev[j] = lf[j]; O.bbPrev[j] = bb[j]; }
         if (pw == 0) { SW_T(6);
 #ifdef S4B_SWEEP_TIMING
-          if ((int)blockIdx.x == SW_TIMED_WG && lane == 0 && t > 0 && t < T) { atomicAdd(&F.tacc[0], 1ull); atomicAdd(&F.tacc[7], (unsigned long long)nb); atomicAdd(&g_sw[72 + (nb < 15 ? nb : 15)], 1ull); }    // [72..87] histogram of the bins per step
+          if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T) { atomicAdd(&F.tacc[0], 1ull); atomicAdd(&F.tacc[7], (unsigned long long)nb); atomicAdd(&g_sw[72 + (nb < 15 ? nb : 15)], 1ull); }    // [72..87] histogram of the bins per step
 #endif
         }
         SW_MARK();
@@ -2624,11 +2624,11 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
   }
   __syncthreads();
 #ifdef S4B_SWEEP_TIMING
-  if ((int)blockIdx.x == SW_TIMED_WG && threadIdx.x < 64 && F.tacc[threadIdx.x]) atomicAdd(&g_sw[threadIdx.x], F.tacc[threadIdx.x]);
+  if ((int)SW_BX == SW_TIMED_WG && threadIdx.x < 64 && F.tacc[threadIdx.x]) atomicAdd(&g_sw[threadIdx.x], F.tacc[threadIdx.x]);
 #endif
   if (F.abort) { SW_KERNARGS(); if (threadIdx.x == 0) { *a.errFlag |= S4B_ERR_INTERNAL | S4B_ERR_I_WAIT; x.status[1] = F.abort; } return; }
 #ifdef S4B_TUNING
-  { SW_KERNARGS(); if (threadIdx.x == 0 && blockIdx.x < 6) x.status[2 + blockIdx.x] = (F.needBig << 24) | (F.paGo << 8) | (bailStep & 0xff); }
+  { SW_KERNARGS(); if (threadIdx.x == 0 && SW_BX < 6) x.status[2 + SW_BX] = (F.needBig << 24) | (F.paGo << 8) | (bailStep & 0xff); }
 #endif
   if (!F.needBig) {
     SW_KERNARGS();
@@ -2642,7 +2642,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
     (void)bailStep;
     const int tn = t;
     const int nc = a.nc;
-    const int G = (int)gridDim.x;
+    const int G = (int)SW_GX;
     double* const partOut = a.partF + (size_t)(t & 1) * 3 * a.binCap * a.gridF;
     const size_t kindStride = (size_t)a.binCap * a.gridF;
     if (ctl) {
@@ -2671,7 +2671,7 @@ __device__ __forceinline__ void sweep_body(BartArrays aKern, SweepArgs xKern) {
       F.last = (k == G - 1) ? 1 : 0;
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #ifdef S4B_TUNING
-      x.status[8 + (blockIdx.x & 3)] = 1000 + k;
+      x.status[8 + (SW_BX & 3)] = 1000 + k;
 #endif
     }
     __syncthreads();
@@ -2722,5 +2722,18 @@ __global__ __launch_bounds__(FBLOCK) void k_sweep_few_sp(BartArrays aKern, Sweep
 __global__ __launch_bounds__(FBLOCK) void k_sweep_w(BartArrays aKern, SweepArgs xKern) { sweep_body<false, true, false, true>(aKern, xKern); }
 #else
 __global__ __launch_bounds__(FBLOCK) void k_sweep_w(BartArrays, SweepArgs xKern) { if (threadIdx.x == 0 && blockIdx.x == 0) *xKern.status = -3; }      // (the build variants with another reduction have no weighted sweep: refused, the host raises an error)
+#endif
+// Batched launches of the solo sweep (the sweep group, dev_hip.hip): workgroup b is member b's one-workgroup sweep, its arguments in slot b.
+// No workgroup of such a launch waits for another one.
+__global__ __launch_bounds__(FBLOCK) void k_sbatch(const unsigned char*) { sweep_body<false, false, false, false, true>(0, 0); }
+__global__ __launch_bounds__(FBLOCK) void k_sbatch_few(const unsigned char*) { sweep_body<false, true, false, false, true>(0, 0); }
+__global__ __launch_bounds__(FBLOCK) void k_sbatch_sp(const unsigned char*) { sweep_body<false, false, true, false, true>(0, 0); }
+__global__ __launch_bounds__(FBLOCK) void k_sbatch_few_sp(const unsigned char*) { sweep_body<false, true, true, false, true>(0, 0); }
+#if !S4B_LINEAR && S4B_WAVERED
+__global__ __launch_bounds__(FBLOCK) void k_sbatch_w(const unsigned char*) { sweep_body<false, true, false, true, true>(0, 0); }
+#else
+__global__ __launch_bounds__(FBLOCK) void k_sbatch_w(const unsigned char* slots) {      // (as k_sweep_w in these variants: refused; the host never batches a weighted member here)
+  if (threadIdx.x == 0) *((const SweepArgs*)(slots + (size_t)blockIdx.x * SW_SLOT_BYTES + SW_SLOT_XOFF))->status = -3;
+}
 #endif
 #endif   // S4B_SWEEP_TU

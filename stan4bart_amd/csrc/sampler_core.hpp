@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/stan4bart_amd.h"
+#include "sweep_group.hpp"
 #include "dev_common.hpp"
 #include "stan_host.hpp"
 
@@ -98,7 +99,7 @@ class SamplerCore {
         }
       }
     }
-    dev_.init_stored(device, P_);
+    dev_.init_stored(device, P_); groupDevice_ = device;
   }
   // stan4bart_exportBARTState (reference src/init.cpp:409-416): needed size; written when the buffer is large enough
   int64_t export_state(void* buf, int64_t cap) const {
@@ -182,7 +183,7 @@ class SamplerCore {
     if (nTest_) bin_matrix(bd->x_test, nTest_, xbinTest);
 
     DevInit di;
-    di.n = (int64_t)n_; di.nTest = (int64_t)nTest_; di.P = P_; di.T = T_; di.nc = nc_; di.device = cc->device;
+    di.n = (int64_t)n_; di.nTest = (int64_t)nTest_; di.P = P_; di.T = T_; di.nc = nc_; di.device = cc->device; groupDevice_ = cc->device;
     di.xbin = xbin.data(); di.xbinTest = nTest_ ? xbinTest.data() : nullptr; di.numCuts = numCuts_.data();
     di.y = sd->y; di.userOffset = hasUserOffset_ ? userOffset_.data() : nullptr; di.weights = weights_.empty() ? nullptr : weights_.data();
     di.model.P = P_; di.model.Pvalid = 0;
@@ -309,7 +310,7 @@ class SamplerCore {
         const bool emit = !lastOnly || iter == numIter - 1;
         if (nTest_ && emit && ((out && out->bart_test) || callback_)) dev_.request_test_fits();
         if (out && emit && out->bart_varcount) dev_.request_var_counts();
-        dev_.sweep_and_stan_inputs(thin_, stan_mode(), wantTrain && emit, cX_.data(), cZ_.data(), &s0_, (wantTrain && emit) ? train.data() : nullptr);
+        sweep_and_stan_inputs(wantTrain && emit, (wantTrain && emit) ? train.data() : nullptr);
         if (timing) { tph[2] += now() - t0; t0 = now(); }
         if (nTest_ && emit && ((out && out->bart_test) || callback_)) dev_.test_fits(test.data());
         if (out && emit) {
@@ -653,7 +654,60 @@ class SamplerCore {
   void counters(int64_t out[3]) { live(); out[0] = model_->gradEvals; out[1] = treeUpdates_; out[2] = dev_.launches(); }
   Dev& dev() { return dev_; }
 
+  // ---- sweep groups (sweep_group.hpp).  A device layer with batched kernels (DevHip) keeps its membership and arrives inside its own
+  // persistent launch; for one without them this class is the member: its sweeps go through the rendezvous of a HostSweepGroup, whose
+  // launch runs each member's sweep in turn.
+  static constexpr bool kNativeGroup = has_native_sweep_group<Dev>::value;
+  ~SamplerCore() { try { leave_group(); } catch (...) {} }
+  static SweepGroup* make_group(int device, int maxMembers) {
+    if constexpr (kNativeGroup) return Dev::group_create(device, maxMembers);
+    else return new HostSweepGroup(device, maxMembers);
+  }
+  void join_group(SweepGroup* g) {
+    if constexpr (kNativeGroup) dev_.join_group(g);
+    else {
+      if (group_) throw std::invalid_argument("sweep_group_join: the sampler is already in a sweep group");
+      if (g->device() != groupDevice_) throw std::invalid_argument("sweep_group_join: the sampler runs on device " + std::to_string(groupDevice_) + ", the group on device " + std::to_string(g->device()));
+      g->join(this); group_ = g;
+    }
+  }
+  void leave_group() {
+    if constexpr (kNativeGroup) dev_.leave_group();
+    else if (group_) { group_->leave(this); group_ = nullptr; }
+  }
+  // Scope of one run(): waited for by the other members while inside, withdrawn on the way out (return or exception)
+  struct GroupRun {
+    SamplerCore& c;
+    explicit GroupRun(SamplerCore& cc) : c(cc) { if (SweepGroup* g = c.group()) g->enter_run(c.group_member(), c.group_eligible()); }
+    ~GroupRun() { if (SweepGroup* g = c.group()) g->exit_run(c.group_member()); }
+    GroupRun(const GroupRun&) = delete;
+    GroupRun& operator=(const GroupRun&) = delete;
+  };
+
  private:
+  SweepGroup* group_ = nullptr;      // (device layers without batched kernels)
+  int groupDevice_ = 0;
+  SweepGroup* group() { if constexpr (kNativeGroup) return dev_.group_; else return group_; }
+  void* group_member() { if constexpr (kNativeGroup) return &dev_; else return this; }
+  bool group_eligible() {
+    if constexpr (kNativeGroup) return dev_.group_eligible();
+    else { int32_t path[2]; dev_.get_tree_path(path); return n_ <= 4096 && (path[0] == 0 || path[0] == 4); }      // (the solo regime of the persistent path)
+  }
+  // the BART sweeps of one Gibbs iteration and the Stan block's inputs behind them
+  void sweep_and_stan_inputs(bool wantTrain, double* train) {
+    if constexpr (!kNativeGroup) {
+      if (group_) {
+        if (!group_eligible()) { dev_.sweep_and_stan_inputs(thin_, stan_mode(), wantTrain, cX_.data(), cZ_.data(), &s0_, train); group_->count_unbatched(thin_); return; }
+        for (int k = 0; k < thin_; ++k) {
+          GroupJob job; job.member = this; job.run = [](void* m) { static_cast<SamplerCore*>(m)->dev_.sweep(1); };
+          group_->arrive(job);
+        }
+        dev_.stan_inputs(stan_mode(), wantTrain, cX_.data(), cZ_.data(), &s0_, train);
+        return;
+      }
+    }
+    dev_.sweep_and_stan_inputs(thin_, stan_mode(), wantTrain, cX_.data(), cZ_.data(), &s0_, train);
+  }
   static constexpr uint32_t STATE_MAGIC = 0x54423453u;   // "S4BT"
   struct Reader {
     const unsigned char* p; size_t n, pos; const char* what = "exported BART state: truncated";

@@ -73,6 +73,7 @@ class Stan4bartFit:
     callback: Optional[np.ndarray] = None   # [len(result), iterations, chains]
     weights: Optional[np.ndarray] = None    # observation weights of the training sample
     k: Optional[np.ndarray] = None          # [iterations, chains] draws of a modeled end-node sensitivity k (bart_args k = chi(...)), else None
+    batch_stats: Optional[dict] = None      # batch_chains=True: the sweep groups' counters summed over the thread batches, else None
 
     # ------------------------------------------------------------------ helpers
     def _get(self, name: str, include_warmup, only_warmup):
@@ -341,11 +342,43 @@ def _stack(chain_results, phase, key, sub=None):
     return np.stack(arrs, axis=-1)
 
 
+class _BatchGroup:
+    """The sweep group of one thread batch of stan4bart(batch_chains=True): made by the first chain that joins (its library and device),
+    left by every chain on its way out, freed after the batch."""
+
+    def __init__(self, size: int):
+        import threading
+        self.size, self.group, self.lock = size, None, threading.Lock()
+
+    def join(self, s, device: int):
+        from .abi import SweepGroup
+        with self.lock:
+            if self.group is None:
+                self.group = SweepGroup(s._lib, s._pfx, device, self.size)
+            self.group.join(s)
+
+    def leave(self, s):
+        with self.lock:
+            if self.group is not None:
+                self.group.leave(s)
+
+    def close(self, total: Optional[dict]) -> Optional[dict]:
+        with self.lock:
+            if self.group is None:
+                return total
+            st = self.group.stats()
+            self.group.free()
+            self.group = None
+        if total is None:
+            return st
+        return {k: total[k] + st[k] for k in st}
+
+
 def stan4bart(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_bart_test=None, X_test=None,
               groups_test: Optional[Sequence[GroupTerm]] = None, offset=None, offset_test=None, offset_type: str = "default",
               family: str = "gaussian", chains: int = 4, seed: Optional[int] = None, iter: int = 2000, warmup: int = 1000,
               keep_warmup: bool = True, make_sampler: Optional[Callable] = None, treatment=None, callback: Optional[Callable] = None,
-              cores: int = 1, **kw) -> Stan4bartFit:
+              cores: int = 1, batch_chains: bool = False, **kw) -> Stan4bartFit:
     """The reference's ``stan4bart()`` after its formula front end (R/stan4bart.R:1-297 -> arrays): runs ``chains``
     chains with the single-threaded seeding rule (R/stan4bart_fit.R:545-554) and packages the draws
     (``package_samples``, R/stan4bart.R:299-455).  With ``bart_args = {"keepTrees": True}`` the samplers stay alive
@@ -358,7 +391,13 @@ def stan4bart(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_bart_test=N
 
     ``cores > 1`` runs the chains concurrently with the reference's parallel seeding rule (R/stan4bart_fit.R:515-533: worker c
     does ``set.seed(sample.int(.Machine$integer.max, chains)[c])``), here as host threads sharing the device: one chain leaves
-    most of an MI355X idle at n = 1e6, four interleaved chains finish about twice as fast as four in a row."""
+    most of an MI355X idle at n = 1e6, four interleaved chains finish about twice as fast as four in a row.
+
+    ``batch_chains=True`` (needs ``cores > 1``) puts each thread batch of chains into one sweep group: while a chain's tree sweep runs
+    on one workgroup (n <= 4 096), the sweeps of the batch's chains go out as one launch, one workgroup per chain.  The draws are
+    those of ``batch_chains=False``; ``fit.batch_stats`` counts the batched launches and the sweeps that went out on their own."""
+    if batch_chains and cores <= 1:
+        raise ValueError("batch_chains=True batches the sweeps of chains run concurrently: it needs cores > 1")
     make_sampler = make_sampler or hip_sampler_factory()
     if treatment is not None:
         if x_bart_test is not None or X_test is not None:
@@ -386,7 +425,7 @@ def stan4bart(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_bart_test=N
     results, samplers = [None] * chains, [None] * chains
     args_box = [None]
 
-    def one_chain(c, chain_rng, sharing=1):
+    def one_chain(c, chain_rng, sharing=1, group=None):
         args = make_sampler_args(y, x_bart, X=X, groups=groups, x_test=x_bart_test, family=family, iter=iter, warmup=warmup,
                                  offset=offset, offset_type=offset_type, keep_fits=True, callback=cb, **kw)
         args_box[0] = args
@@ -394,6 +433,8 @@ def stan4bart(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_bart_test=N
         s = make_sampler(args, chain_rng.state)
         r = {}
         try:
+            if group is not None:
+                group.join(s, args.device)
             if sharing > 1 and hasattr(s, "set_device_sharing"):
                 s.set_device_sharing(sharing)                 # host threads that share the GPU while this chain runs (its batch)
             names_box[:] = [s.stan_par_names()]
@@ -405,7 +446,11 @@ def stan4bart(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_bart_test=N
             qr_back_transform(args, r)       # stan_args = {"QR": True}: beta rows back to the design's scale (R/stan4bart_fit.R:560-570)
             r["range.bart"] = s.get_bart_data_range()
             chain_rng.state = s.get_r_rng_state()
+            if group is not None:
+                group.leave(s)
         except Exception:
+            if group is not None:
+                group.leave(s)
             s.free()
             raise
         if keep_trees:
@@ -414,6 +459,7 @@ def stan4bart(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_bart_test=N
             s.free()
         results[c] = r
 
+    batch_stats = None
     if cores <= 1 or chains == 1:
         try:
             for c in range(chains):        # one stream continued from chain to chain (R/stan4bart_fit.R:545-554)
@@ -428,17 +474,22 @@ def stan4bart(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_bart_test=N
         seeds = chain_seeds(int(rng.sample_int(INT_MAX, 1)[0]) if seed is None else seed, chains)
         errors = []
 
-        def guarded(c, sharing):
+        def guarded(c, sharing, group):
             try:
-                one_chain(c, RRng(int(seeds[c])), sharing)
+                one_chain(c, RRng(int(seeds[c])), sharing, group)
             except Exception as e:   # surfaced after the join
                 errors.append(e)
         pending = list(range(chains))
         while pending:
             batch, pending = pending[:cores], pending[cores:]
-            th = [threading.Thread(target=guarded, args=(c, len(batch))) for c in batch]
-            [t.start() for t in th]
-            [t.join() for t in th]
+            group = _BatchGroup(len(batch)) if batch_chains else None
+            try:
+                th = [threading.Thread(target=guarded, args=(c, len(batch), group)) for c in batch]
+                [t.start() for t in th]
+                [t.join() for t in th]
+            finally:
+                if group is not None:
+                    batch_stats = group.close(batch_stats)
         if errors:
             for sm in samplers:
                 if sm is not None:
@@ -469,4 +520,4 @@ def stan4bart(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_bart_test=N
         terms=terms, terms_test=terms_test, offset=None if offset is None else np.asarray(offset, dtype=np.float64),
         offset_test=None if offset_test is None else np.asarray(offset_test, dtype=np.float64), offset_type=offset_type,
         range_bart=np.stack([r["range.bart"] for r in results], axis=1), samplers=samplers, callback=smp["callback"],
-        weights=None if kw.get("weights") is None else np.asarray(kw["weights"], dtype=np.float64), k=smp["k"])
+        weights=None if kw.get("weights") is None else np.asarray(kw["weights"], dtype=np.float64), k=smp["k"], batch_stats=batch_stats)
