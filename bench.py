@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the stan4bart Gibbs hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 Metric (BASELINE.json): Gibbs iterations / second at n = 1e6, p = 50, ntree = 200 — BASELINE config 3:
 Friedman data, formula y ~ bart(. - X4 - z - g.1 - g.2) + X4 + z + (1 + X4 | g.1) + (1 | g.2), one chain per GPU.
@@ -14,14 +14,19 @@ What is timed is a RUNNING chain in its STATIONARY regime, in the reference's ph
 disengage adaptation, sample): `--burn-in` untimed warm-up iterations with adaptation engaged (default 1000 — the reference's default
 fit is 1000 warm-up + 1000 sampling iterations), adaptation is disengaged, then W untimed and exactly K timed iterations of the SAMPLING
 phase follow.  At this size the chain needs several hundred iterations before NUTS reaches the tree depth it then keeps (~1000 leapfrogs
-per transition: DESIGN.md 8); a short burn-in times a transient that is 30 times cheaper in leapfrogs.  `config.stationarity` therefore
-compares the leapfrogs per iteration of the timed window with those of the next `--mode-iters` iterations of the same chain and says
-whether they agree within 20 %; `value` is only a stationary figure when it says so.
+per transition: DESIGN.md 8); a short burn-in times a transient that is 30 times cheaper in leapfrogs.  With `--full`, `config.stationarity`
+therefore compares the leapfrogs per iteration of the timed window with those of the next `--mode-iters` iterations of the same chain and
+says whether they agree within 20 %; `value` is only a stationary figure when it says so.
 
 `--dump-outputs DIR` writes what the last timed iteration returned (dump_outputs) as .npy files: the inputs and seeds depend on the
 arguments alone, so two builds can be compared output for output.
 
-Extra objects on the same JSON line:
+A plain run does what the headline needs and nothing else: design, sampler, burn-in, W + K sampling iterations, the dump, the line.
+`--full` times the same iterations of the same chain, then measures and checks everything else; among the objects this adds to the
+line (the options that narrow or size these legs — `--no-*`, `--mode-iters`, `--profile-sweeps`, `--cpu-iters`, `--target-*`, `--c5-*` —
+act only under `--full`):
+  config.stationarity see above
+  scaling_efficiency_vs_committed_n1   N > 1: against the committed N = 1 line of the same sources (profiles/bench_n1_reference.json)
   roofline            dominant kernel of the sweep, HIP-event timing on the sampler's own stream, against 8 TB/s HBM
   per_chain_hmc_mode1 the same chain continued for K more timed iterations with one O(N) device evaluation per leapfrog
                       (the reference's cost model); the headline uses sufficient statistics gathered once per iteration
@@ -382,6 +387,9 @@ def main():
     ap.add_argument("--n", "--num-obs", dest="n", type=int, default=1_000_000)   # (--num-obs: torchrun's own parser trips over a bare --n)
     ap.add_argument("--p", type=int, default=50)
     ap.add_argument("--trees", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg: stationarity, both gradient modes, rooflines, the CPU baseline, "
+                         "the roofline-target size, the extra BASELINE configs (the options below narrow or size these legs)")
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true")
@@ -466,7 +474,8 @@ def main():
     # ---- phase 2: sampling.  W untimed, then exactly K timed Gibbs iterations
     if a.warmup > 0:
         sampler.run(a.warmup, False, 0)
-    state_after_burn_in = sampler.get_state() if (rank == 0 and world == 1 and not a.emul and not (a.no_cpu_baseline and a.no_hmc_mode1)) else None
+    # (--full: the chain's state where the timed region begins, for the legs that go back to it; reading it changes nothing in the chain)
+    state_after_burn_in = sampler.get_state() if (a.full and rank == 0 and world == 1 and not a.emul and not (a.no_cpu_baseline and a.no_hmc_mode1)) else None
     barrier()
     c0, s0 = sampler.get_counters(), sampler.get_nuts_stats()
     t0 = time.perf_counter()
@@ -501,7 +510,7 @@ def main():
                    "n_leapfrog_per_step": (sampler.get_nuts_stats()["sum_n_leapfrog"] - m0["sum_n_leapfrog"]) / a.steps,
                    "note": "hmc_mode 1 over the SAME iterations as the headline (chain put back to the state at the start of the timed region)"}
         sampler.set_hmc_mode(hmc_mode)
-    if not a.no_hmc_mode1 and not a.emul:
+    if a.full and not a.no_hmc_mode1 and not a.emul:
         state0 = sampler.get_state()
         legs = {}
         for mode in (0, 1):
@@ -530,7 +539,7 @@ def main():
     summ = all_gather_array(np.array([float(out["bart"]["sigma"][-1]), t_design - t_start, t_created - t_design, dt, float(len(cores))]))
 
     prof = lf = probe = None
-    if rank == 0 and not a.emul:
+    if a.full and rank == 0 and not a.emul:
         prof = sampler.profile_sweep(a.profile_sweeps)
         lf = sampler.profile_leapfrog(20)
         po = (ctypes.c_double * 4)()   # measured streaming ceiling of this device (read-only and in-place update over 1 GB)
@@ -550,7 +559,7 @@ def main():
         sampler.set_trace(False)
     sampler.free()
     target = None
-    if world == 1 and a.target_n > 0 and a.target_n != a.n and not a.emul:
+    if a.full and world == 1 and a.target_n > 0 and a.target_n != a.n and not a.emul:
         target = target_roofline_leg(lib, a.target_n, a.p, a.trees, local_rank, a.profile_sweeps, a.target_burn_in)
 
     if rank == 0:
@@ -583,7 +592,7 @@ def main():
                        "setup_seconds_per_rank": {"design (rank 0 generates, others load)": [float(s[1]) for s in summ],
                                                   "create (binning, upload, init)": [float(s[2]) for s in summ]}},
         }
-        if world > 1:
+        if a.full and world > 1:
             # scaling efficiency against the committed single-GPU line of this round (the driver computes its own from its N = 1 run)
             try:
                 with open(os.path.join(ROOT, "profiles", "bench_n1_reference.json")) as f:
@@ -666,7 +675,7 @@ def main():
                                              f"after the burn-in (adapted step size and metric; {lfc:.1f} leapfrogs per iteration, each O(N) as in the reference), "
                                              f"{secs:.1f} s of single-thread CPU time, host has {os.cpu_count()} cores",
                                    "reference_R_package": reference_r_leg(n, a.p, a.trees, a.cpu_iters)}
-        if world == 1 and not a.no_extra_configs and not a.emul:
+        if a.full and world == 1 and not a.no_extra_configs and not a.emul:
             # BASELINE configs 1 and 2: small and quick, reported beside the headline
             from stan4bart_amd import GroupTerm, generate_friedman_data, make_sampler_args
             olib = oracle_lib()

@@ -135,6 +135,24 @@ def test_bench_launches_its_own_ranks(emul_lib):
     assert rec["n_gpus"] == 2 and rec["config"]["chains"] == 2 and len(rec["per_chain_by_rank"]) == 2
 
 
+def test_bench_full_is_opt_in(emul_lib):
+    """a plain N-rank run prints the headline alone; `--full` (passed on to every rank) adds the comparison with the committed N = 1 line"""
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--burn-in", "4", "--n", "300", "--p", "10",
+           "--trees", "5", "--emul"]
+    recs = []
+    for extra in ([], ["--full"]):
+        out = subprocess.run(cmd + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=dict(_clean_env(), OMP_NUM_THREADS="1"), cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        recs.append(json.loads(lines[0]))
+    plain, full = recs
+    assert "scaling_efficiency_vs_committed_n1" not in plain and "scaling_efficiency_vs_committed_n1" in full
+    assert plain["config"]["sigma_last"] == full["config"]["sigma_last"]
+
+
 def test_bench_refuses_more_gpus_than_visible():
     """--gpus N with fewer than N visible GPUs exits non-zero — it must never run fewer chains than asked for and print n_gpus: 1"""
     import subprocess

@@ -5,7 +5,7 @@
 # Steps (any subset, in the order given), everything under gpurun_out/<tag>/:
 #   tests        the whole GPU suite (per-test timeout: a launch that never returns must not take the box with it)
 #   quick        parity + fuzz + configs only
-#   bench        python bench.py (the driver's line)               -> bench_default.json
+#   bench        python bench.py --full (every leg)                 -> bench_default.json
 #   benchlite    the headline only (no CPU leg, no extra configs)  -> bench_lite.json
 #   probe        tools/step_probe.py --iters 300 at n = 1e6 (stationary sweep)   -> probe.json
 #   ab <lib>     A/B/A/B of the product library against stan4bart_amd/csrc/<lib> with step_probe --iters 300
@@ -23,7 +23,7 @@ while [ $# -gt 0 ]; do
   case $step in
     tests) timeout 2400 python -m pytest tests -m gpu -x -q $PT > "$O/pytest.log" 2>&1; echo "tests rc $?"; tail -n 3 "$O/pytest.log" ;;
     quick) timeout 1500 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fuzz.py tests/test_gpu_configs.py tests/test_gpu_large.py tests/test_gpu_busy.py -m gpu -x -q $PT > "$O/pytest_quick.log" 2>&1; echo "quick rc $?"; tail -n 3 "$O/pytest_quick.log" ;;
-    bench) timeout 1500 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err"; echo "bench rc $?"; cut -c1-300 "$O/bench_default.json"; tail -n 3 "$O/bench_default.err" ;;
+    bench) timeout 1500 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"; echo "bench rc $?"; cut -c1-300 "$O/bench_default.json"; tail -n 3 "$O/bench_default.err" ;;
     benchlite) timeout 900 python bench.py --no-cpu-baseline --no-extra-configs --target-n 0 --no-hmc-mode1 --mode-iters 0 > "$O/bench_lite.json" 2> "$O/bench_lite.err"; echo "benchlite rc $?"; cut -c1-300 "$O/bench_lite.json" ;;
     probe) timeout 600 python tools/step_probe.py --iters 300 --sweeps 5 > "$O/probe.json" 2> "$O/probe.err"; cat "$O/probe.json" ;;
     ab) lib=$1; shift

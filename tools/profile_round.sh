@@ -20,7 +20,7 @@ for N in 1000000 10000000; do
   # (every pass — kernel trace AND counters — runs the chain the benchmark times: past its burn-in.  A cold chain accepts more moves, a stationary one
   # carries more bins per step: until round 5 the counter passes and n = 1e7 used a 30-iteration burn-in)
   TRACEBURN=$BURN7; [ "$N" = "1000000" ] && TRACEBURN=$BURN
-  COMMON="--n $N --no-cpu-baseline --no-extra-configs --no-hmc-mode1 --target-n 0 --mode-iters 0 --burn-in $TRACEBURN"
+  COMMON="--n $N --full --no-cpu-baseline --no-extra-configs --no-hmc-mode1 --target-n 0 --mode-iters 0 --burn-in $TRACEBURN"
   rm -rf "$OUT/prof_n$N" "$OUT/pmc_fetch_n$N" "$OUT/pmc_write_n$N"
   timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_n$N" -- python3 "$ROOT/bench.py" $COMMON --steps 20 --warmup 5 > "$OUT/bench_prof_n$N.log" 2>&1
   python3 "$ROOT/tools/rocpd_summary.py" "$(newest_db "$OUT/prof_n$N")" "$ROOT/profiles/${TAG}_rocprofv3_prof_n$N.txt"
@@ -34,7 +34,7 @@ done
 echo "$TRAFFIC}" > "$ROOT/profiles/pmc_traffic.json"
 # the fused launch per tree (k_step: the automatic choice of rounds 2-3, now the hand-over target of the persistent sweep): per-kernel durations
 rm -rf "$OUT/prof_fused"
-timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_fused" -- python3 "$ROOT/bench.py" --n 1000000 --no-cpu-baseline --no-extra-configs --target-n 0 --no-hmc-mode1 --mode-iters 0 --burn-in 150 --steps 20 --warmup 5 --tree-path fused > "$OUT/bench_prof_fused.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_fused" -- python3 "$ROOT/bench.py" --n 1000000 --full --no-cpu-baseline --no-extra-configs --target-n 0 --no-hmc-mode1 --mode-iters 0 --burn-in 150 --steps 20 --warmup 5 --tree-path fused > "$OUT/bench_prof_fused.log" 2>&1
 python3 "$ROOT/tools/rocpd_summary.py" "$(newest_db "$OUT/prof_fused")" "$ROOT/profiles/${TAG}_rocprofv3_prof_fused_n1000000.txt"
 # the box's repository copy is scratch: hand the summaries back through gpurun_out/
 mkdir -p "$OUT/profiles" && cp "$ROOT"/profiles/${TAG}_rocprofv3_* "$ROOT/profiles/pmc_traffic.json" "$OUT/profiles/"
