@@ -2249,13 +2249,16 @@ class DevHip {
         constexpr bool weightedSweepBuilt = !S4B_LINEAR && S4B_WAVERED;      // (the build variants with another reduction of the statistics have no k_sweep_w: weighted samplers take the per-tree kernels there)
         size_t staticLds = 40 * 1024;
         if (weighted_ && weightedSweepBuilt) { hipFuncAttributes fa; HIP_OK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_sweep_w))); staticLds = fa.sharedSizeBytes + 512; }      // (its static part: tables + 32 KiB of weights)
-        const bool common = stepOk && !(weighted_ && (splitProbs_ || !weightedSweepBuilt)) && a.gridF >= 2 && a.gridF <= 256 && a.gridF <= prop.multiProcessorCount &&
-                            sweep_lds_bytes() + staticLds <= 160 * 1024;
         if (weighted_) {      // the power of two that brings the largest weight into (0.5, 1]
           double mx = 0.0; for (int64_t i = 0; i < n_; ++i) mx = std::max(mx, d.weights[i]);
           int e = 0; if (mx > 0.0 && std::isfinite(mx)) (void)std::frexp(mx, &e);
           wScale_ = std::ldexp(1.0, -e); wUnscale_ = std::ldexp(1.0, e);
         }
+        // (a subnormal largest weight has no such power of two: 2^-e overflows.  Those samplers stay on the per-tree kernels, which sum the weights in
+        // plain double)
+        const bool wScaleOk = !weighted_ || (std::isfinite(wScale_) && wScale_ > 0.0 && wUnscale_ > 0.0);
+        const bool common = stepOk && !(weighted_ && (splitProbs_ || !weightedSweepBuilt || !wScaleOk)) && a.gridF >= 2 && a.gridF <= 256 &&
+                            a.gridF <= prop.multiProcessorCount && sweep_lds_bytes() + staticLds <= 160 * 1024;
         sweepRegsOk_ = common && nQuads <= (int64_t)(a.gridF - 1) * SW_PT * SW_PF;
         sweepStreamOk_ = common && !splitProbs_ && !weighted_ && (n_ + a.gridF - 2) / (a.gridF - 1) + 4 * SW_PT < (int64_t)1 << 21;
         sweepOk_ = sweepRegsOk_ || sweepStreamOk_;

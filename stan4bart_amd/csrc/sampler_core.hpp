@@ -132,7 +132,8 @@ class SamplerCore {
     if (sd->has_weights) {
       if (!sd->weights) throw std::invalid_argument("has_weights = 1 but weights is NULL");
       if (cc->is_binary) throw std::invalid_argument("observation weights are not available for binary responses");
-      for (int64_t i = 0; i < sd->N; ++i) if (!(sd->weights[i] > 0.0)) throw std::invalid_argument("weights must be positive");
+      // (+inf passes `w > 0`: the likelihood sums of both sides would turn non-finite, and the persistent sweep's weight scale with them)
+      for (int64_t i = 0; i < sd->N; ++i) if (!(sd->weights[i] > 0.0) || !std::isfinite(sd->weights[i])) throw std::invalid_argument("weights must be positive and finite");
       weights_.assign(sd->weights, sd->weights + sd->N);
     }
     if (sd->has_intercept) throw std::invalid_argument("has_intercept = 1 is not supported (BART supplies the intercept)");

@@ -55,3 +55,39 @@ def large_case(seed, n=None, iters=None, deep=None, k_chi=None, trees=None, spli
     if bart_args.get("power") == 0.3:
         args.node_capacity = 1024
     return args, dict(n=n, p=p, binary=binary, **{k: v for k, v in bart_args.items() if k != "split.probs"}, split_probs=bool(split_probs), weights=w is not None)
+
+
+def sized_case(n, seed=0, p=10, trees=8, iters=(2, 8), deep=False, weights=False, k_chi=None, split_probs=False, binary=False, joint=False, **kw):
+    """Sampler arguments at the sizes that pick the fused (k_step) and the two-kernel (k_tree + k_control) tree updates (tests/test_gpu_sizes.py).
+    numpy's generator (generate_friedman_data's R-compatible stream would take minutes at n = 1e7), p uniform covariates with n.cuts = 100: at these
+    sizes every cut of an ordinary tree leaves thousands of observations on both sides, so no proposal can empty a leaf (the reference's empty-leaf
+    rule, DESIGN.md 7, stays out of reach).  BART block only unless `joint` (then a fixed effect and a random intercept of 5 groups: the Stan block's O(N) sums).
+    `deep`: base 0.99, power 0.3, k 0.3 and 1024 node slots (trees of tens of leaves: more than 8 bins per proposal, more than 64 node slots).
+    `weights`: observation weights of O(1).  `k_chi`: (df, scale) of a modeled k.  `split_probs`: cgm(split.probs = ).  `binary`: probit latents (needs `joint`: a probit model of BART alone is refused as improper).  Other keywords go to make_sampler_args."""
+    from stan4bart_amd import GroupTerm, make_sampler_args
+    g = np.random.default_rng(800000 + seed)
+    xb = np.empty((n, p), order="F")
+    for j in range(p):
+        xb[:, j] = g.random(n)
+    f = 10.0 * np.sin(np.pi * xb[:, 0] * xb[:, 1]) + 20.0 * (xb[:, 2] - 0.5) ** 2 + 10.0 * xb[:, 3] + 5.0 * xb[:, 4]
+    y = f + g.standard_normal(n)
+    X, groups = None, []
+    if joint:
+        X = g.random(n)[:, None]
+        y = y + 2.0 * X[:, 0]
+        groups = [GroupTerm(g.integers(1, 6, size=n), None, "g.1")]
+    if binary:
+        y = (y > np.median(y)).astype(np.float64)
+    bart_args = {"n.trees": int(trees), "n.cuts": 100}
+    if deep:
+        bart_args.update(base=0.99, power=0.3, k=0.3)
+    if k_chi is not None:
+        bart_args["k"] = ("chi", float(k_chi[0]), float(k_chi[1]))
+    if split_probs:
+        bart_args["split.probs"] = [float(v) for v in g.choice([0.05, 0.5, 1.0, 3.0, 8.0], size=p)]
+    w = g.uniform(0.25, 4.0, n) if weights else None
+    args = make_sampler_args(y, xb, X=X, groups=groups, family="binomial" if binary else "gaussian", iter=iters[1], warmup=iters[0],
+                             bart_args=bart_args, weights=w, **kw)
+    if deep:
+        args.node_capacity = 1024
+    return args

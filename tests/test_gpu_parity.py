@@ -341,6 +341,26 @@ def test_observation_weights_on_the_full_grid(oracle_lib, hip_lib, n, T, scale, 
         assert inside == sweeps * T and early > 0.3 * inside, b["sweep_spec"]
 
 
+@pytest.mark.parametrize("scale,want", [(1e-300, "persistent"), (1e-310, "fused"), (4e-320, "fused")])
+def test_observation_weights_at_the_bottom_of_the_double_range(oracle_lib, hip_lib, scale, want):
+    """k_sweep_w scales the weights by the power of two that brings the largest into (0.5, 1]: 2^997 for weights of 1e-300.  A subnormal largest
+    weight has no such power of two (2^-e overflows), so those samplers take the per-tree kernels, which sum the weights in plain double; both give
+    the oracle's chain."""
+    w = np.random.default_rng(9).uniform(0.5, 2.0, 400) * scale
+    a = run_chain(oracle_lib, "orc_", friedman_case(n=400, T=10, warmup=5, iter=12, weights=w)[0])
+    b = run_chain(hip_lib, "s4b_", friedman_case(n=400, T=10, warmup=5, iter=12, weights=w)[0])
+    assert b["tree_path"] == ("auto", want), b["tree_path"]
+    assert_chain_parity(a, b)
+
+
+@pytest.mark.parametrize("bad", [np.inf, np.nan])
+def test_non_finite_weights_are_refused_on_the_device(hip_lib, bad):
+    w = np.ones(100)
+    w[7] = bad
+    with pytest.raises(RuntimeError, match="weights must be positive and finite"):
+        run_chain(hip_lib, "s4b_", friedman_case(weights=w)[0])
+
+
 @pytest.mark.parametrize("P", [100, 140])
 def test_config5_shape_many_predictors_and_groups(oracle_lib, hip_lib, P):
     """BASELINE config 5 shape at reduced n: P = 100 predictors (140: beyond the two register tables), 200 groups with

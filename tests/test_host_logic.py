@@ -100,6 +100,24 @@ def test_error_reporting(emul_lib):
         run_chain(emul_lib, "emu_", args)
 
 
+@pytest.mark.parametrize("bad", [np.inf, np.nan, -np.inf])
+def test_non_finite_weights_are_refused_at_create(emul_lib, bad):
+    """`w > 0` lets +inf through: the likelihood sums would turn non-finite, and the persistent sweep's weight scale with them."""
+    args, _ = friedman_case()
+    args.weights = np.ones(100)
+    args.weights[41] = bad
+    with pytest.raises(RuntimeError, match="weights must be positive and finite"):
+        run_chain(emul_lib, "emu_", args)
+
+
+def test_subnormal_weights_match_the_oracle(oracle_lib, emul_lib):
+    """weights of 1e-310, the largest of them subnormal (the device layer's weight scale has no power of two for them: per-tree kernels)."""
+    w = np.random.default_rng(9).uniform(0.5, 2.0, 400) * 1e-310
+    a = run_chain(oracle_lib, "orc_", friedman_case(n=400, T=10, warmup=5, iter=12, weights=w)[0])
+    b = run_chain(emul_lib, "emu_", friedman_case(n=400, T=10, warmup=5, iter=12, weights=w)[0])
+    assert_chain_parity(a, b)
+
+
 def test_interface_version_is_checked_at_create(emul_lib, oracle_lib):
     """s4b_bart_control and s4b_results have grown fields over the revisions and carry no size field: create() refuses a caller whose header is not
     this one's (the word was `reserved`, 0, in the older headers) before it reads any newer field."""
