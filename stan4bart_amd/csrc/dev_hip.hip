@@ -2249,18 +2249,32 @@ class DevHip {
         constexpr bool weightedSweepBuilt = !S4B_LINEAR && S4B_WAVERED;      // (the build variants with another reduction of the statistics have no k_sweep_w: weighted samplers take the per-tree kernels there)
         size_t staticLds = 40 * 1024;
         if (weighted_ && weightedSweepBuilt) { hipFuncAttributes fa; HIP_OK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_sweep_w))); staticLds = fa.sharedSizeBytes + 512; }      // (its static part: tables + 32 KiB of weights)
+        double wMin = 0.0, wMax = 0.0;
         if (weighted_) {      // the power of two that brings the largest weight into (0.5, 1]
-          double mx = 0.0; for (int64_t i = 0; i < n_; ++i) mx = std::max(mx, d.weights[i]);
-          int e = 0; if (mx > 0.0 && std::isfinite(mx)) (void)std::frexp(mx, &e);
+          wMin = d.weights[0]; for (int64_t i = 0; i < n_; ++i) { wMax = std::max(wMax, d.weights[i]); wMin = std::min(wMin, d.weights[i]); }
+          int e = 0; if (wMax > 0.0 && std::isfinite(wMax)) (void)std::frexp(wMax, &e);
           wScale_ = std::ldexp(1.0, -e); wUnscale_ = std::ldexp(1.0, e);
         }
         // (a subnormal largest weight has no such power of two: 2^-e overflows.  Those samplers stay on the per-tree kernels, which sum the weights in
         // plain double)
         const bool wScaleOk = !weighted_ || (std::isfinite(wScale_) && wScale_ > 0.0 && wUnscale_ > 0.0);
-        const bool common = stepOk && !(weighted_ && (splitProbs_ || !weightedSweepBuilt || !wScaleOk)) && a.gridF >= 2 && a.gridF <= 256 &&
+        // (the scaling is exact, the rounding of every partial to the 2^-55 quantum of the exchange words is not: a workgroup's partial of a bin that
+        // holds only the lightest observations is at least wMin * wScale > wMin / wMax / 2, so it is off by at most 2^-56 / (wMin / wMax / 2) =
+        // 2^-55 * wMax / wMin relative, and so is the bin's total, a sum of such partials (the weights are positive).  With wMin / wMax >= 2^-30 that
+        // is 2^-25 = 3.0e-8 of every weighted sum, 1/33 of the 1e-6 to which the chain matches the double sums of k_step / k_tree / the oracle; a
+        // wider range of weights takes the per-tree kernels: tests/test_gpu_exchange.py)
+        const bool wRangeOk = !weighted_ || wMin >= std::ldexp(wMax, -30);
+        const bool common = stepOk && !(weighted_ && (splitProbs_ || !weightedSweepBuilt || !wScaleOk || !wRangeOk)) && a.gridF >= 2 && a.gridF <= 256 &&
                             a.gridF <= prop.multiProcessorCount && sweep_lds_bytes() + staticLds <= 160 * 1024;
         sweepRegsOk_ = common && nQuads <= (int64_t)(a.gridF - 1) * SW_PT * SW_PF;
-        sweepStreamOk_ = common && !splitProbs_ && !weighted_ && (n_ + a.gridF - 2) / (a.gridF - 1) + 4 * SW_PT < (int64_t)1 << 21;
+        // (the streaming pass: pass workgroup b of NP = gridF - 1 owns the blocks of SW_PT quads b, b + NP, b + 2 NP, ..., i.e. at most
+        // ceil(ceil(nQuads / SW_PT) / NP) blocks of 4 SW_PT observations, and adds its counts into copy b % XC_COPIES, which ceil(NP / XC_COPIES) pass
+        // workgroups share (the control workgroup adds count 0).  The count field of the exchange words holds 21 bits: fewer than 2^16 observations
+        // per workgroup and at most 32 workgroups per copy, i.e. at most 63 blocks per workgroup: n <= 255 * 63 * 1 024 = 16 450 560 with 255 of them)
+        const int64_t streamNP = a.gridF - 1, streamBlocks = (nQuads + SW_PT - 1) / SW_PT;
+        const int64_t streamPerWg = (streamBlocks + streamNP - 1) / streamNP * 4 * SW_PT, streamPerCopy = (streamNP + XC_COPIES - 1) / XC_COPIES;
+        const bool streamCountOk = streamPerWg < ((int64_t)1 << 16) && streamPerCopy * streamPerWg <= ((int64_t)1 << 21) - 1;
+        sweepStreamOk_ = common && !splitProbs_ && !weighted_ && streamCountOk;
         sweepOk_ = sweepRegsOk_ || sweepStreamOk_;
         // at most 4096 observations: ONE workgroup holds them all and does the control duties too (no exchange: dev_sweep.inc "solo")
         sweepSolo_ = nQuads <= (int64_t)SW_PT * SW_PF;

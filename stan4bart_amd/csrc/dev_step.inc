@@ -40,8 +40,10 @@ constexpr int F_GRID_MAX = 640;      // partials per bin the reducers combine (t
 // deterministic, and a reader fetches XC_COPIES * 2 nb words instead of one partial per workgroup and bin:
 //   word 0: [arrivals : 6][ rint(s * 2^24) + 2^52                               : 58]
 //   word 1: [arrivals : 6][count : 21][ rint((s - rint(s 2^24) 2^-24) * 2^55) + 2^31 : 37]
-// |s| < 2^27 (checked; the partial residuals of a rescaled response are O(1)), at most 32 workgroups per copy, at most 2^16
-// observations per workgroup: no field can carry into its neighbour.  Resolution 2^-55 absolute per partial.
+// |s| < 2^27 (checked; the partial residuals of a rescaled response are O(1): DESIGN.md 5.0), at most 32 workgroups per copy, fewer than
+// 2^16 observations per workgroup (at most 4 096 with the residual in registers; the streaming pass: dev_hip.hip, streamCountOk), so at most
+// 2^21 - 1 per copy: no field can carry into its neighbour.  Resolution 2^-55 absolute per partial (observation weights: relative to a bin's
+// sums, 2^-55 * max / min weight, at most 2^-25 — dev_hip.hip, wRangeOk).
 constexpr int XC_COPIES = 8, XC_WORDS = 128, XC_RING = 4;      // copies; words per copy (2 per bin, 64 bins); ring of exchange buffers
 constexpr int XC_BUF_WORDS = XC_COPIES * XC_WORDS;
 // (two rings side by side: buffers 0 .. XC_RING-1 take what a step publishes first — speculatively, before its verdict, in the persistent

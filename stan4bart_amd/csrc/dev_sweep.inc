@@ -499,7 +499,9 @@ __device__ __forceinline__ int sweep_fresh_lane() {
 // (WT — observation weights, k_sweep_w: wq = this thread's sixteen weights in LDS (quad j at wq + j * SW_PT * 4; 0 beyond n), the sums become sums of
 // w (r + mu), and a third statistic per bin, the sum of the weights, travels as bin nbAll + k of the same exchange — sum in the sum field, count 0 —: the
 // step then exchanges 2 nbAll "bins", which is why such a launch takes trees of at most 32 bins.  Both are published times wScale, a power of two that brings
-// the largest weight into (0.5, 1]: the fixed-point words hold sums of O(1) terms; the gathering side multiplies by its inverse.  Exact either way.)
+// the largest weight into (0.5, 1]: the fixed-point words hold sums of O(1) terms; the gathering side multiplies by its inverse.  The scaling is exact
+// both ways; the rounding of each partial to the 2^-55 quantum is not, and is a relative error of up to 2^-55 * max / min weight of a bin's sums: the host
+// keeps samplers whose weights span more than 2^30 off this kernel — dev_hip.hip, wRangeOk.)
 template <int NB, bool SKIP, bool LIN, bool WT = false, bool BATCH = false>
 __device__ __forceinline__ bool sweep_stats(const BartArrays& a, const SweepLds& L, PassBar& bar, const double (&r)[SW_PF][4], const lfq_t (&lf)[SW_PF], const NodeS* __restrict__ Ssel,
                                             const unsigned (&bb)[SW_PF], int64_t q0, int64_t stride, int64_t nQuads, int base, unsigned long long* xcur, double* part_,
@@ -1028,8 +1030,8 @@ __device__ __forceinline__ void stream_pass(const BartArrays& a, const SweepLds&
     }
   }
 }
-// (the counts of a workgroup must fit the 21-bit field of the exchange words: at most 2^21 - 1 observations per pass workgroup, i.e.
-// n <= 5.3e8 with 255 of them; the host checks it)
+// (the counts of a copy must fit the 21-bit field of the exchange words: fewer than 2^16 observations per pass workgroup, at most 32 pass
+// workgroups per copy, i.e. n <= 16 450 560 with 255 of them; the host checks it: dev_hip.hip, streamCountOk)
 template <bool APPLY, bool STATS>
 __device__ __forceinline__ void stream_pass_n(int nbThis, const BartArrays& a, const SweepLds& L, PassBar& bar, const StreamStep& st, int tS, int tA, int64_t q0, int64_t stride,
                                               int64_t nQuads, unsigned long long* xcur, double* part, bool alsoPart, int pw, int lane) {
