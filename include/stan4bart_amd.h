@@ -267,13 +267,14 @@ int S4B_FN(predict_bart_offset)(s4b_sampler* s, const double* x_test, int64_t n_
  *           response with the offset removed)
  *   per tree: int32 num_nodes, num_leaves; int32 node[num_nodes][2] in preorder ({var, split} internal, {-1, n_obs} leaf);
  *             double mu[num_leaves] in DFS order
+ *   latent mode 1 only: uint64 key, uint64 draw index of the parallel latents (s4b_set_latent_mode)
  * get_state: call with buf = NULL (or cap too small) to learn the size. */
 #define S4B_STATE_MAGIC 0x53423453u /* "S4BS" */
 typedef struct {
   uint32_t magic, version;   /* S4B_STATE_MAGIC, 1 */
   int64_t n;
   int32_t n_trees, num_unconstrained, is_binary, p;
-  int64_t reserved[2];       /* [0]: bit pattern of the current k (a double) when k is modeled, else 0 */
+  int64_t reserved[2];       /* [0]: bit pattern of the current k (a double) when k is modeled, else 0; [1]: latent mode (set_latent_mode) */
 } s4b_state_header;
 int S4B_FN(get_state)(s4b_sampler* s, void* buf, int64_t cap, int64_t* size);
 int S4B_FN(set_state)(s4b_sampler* s, const void* buf, int64_t size);
@@ -331,6 +332,16 @@ int S4B_FN(get_sweep_busy)(s4b_sampler* s, int64_t* out);
  * has no Gram matrix and stays in mode 1. */
 int S4B_FN(set_hmc_mode)(s4b_sampler* s, int32_t mode);
 int S4B_FN(get_hmc_mode)(s4b_sampler* s, int32_t* mode);
+/* extension: how the probit latents of a binary response are drawn.  0 = exact (default): dbarts' truncated normals from R's stream, the
+ * reference's chain bit for bit.  1 = parallel: every latent drawn independently and exactly from N(mean, 1) truncated by y, one device thread
+ * per observation, from Philox4x32-10 under a 64-bit key derived from the generator state and seed given to create (R's stream is not used
+ * for it; tree proposals and a modeled k still are).  A different chain with the same stationary distribution, not the reference's chain;
+ * it is identical on every tree path, in sweep groups and from run to run.  Set it after create and before the first run (the initial sweep
+ * inside create draws its latents exactly); mode 1 is refused for a continuous response and by a device layer without the parallel draw.
+ * The state of get_state carries the mode (header reserved[1]) and, in mode 1, 16 more bytes at its end: uint64 key, uint64 draw index;
+ * set_state refuses a state of the other mode.  DESIGN.md 5.4b. */
+int S4B_FN(set_latent_mode)(s4b_sampler* s, int32_t mode);
+int S4B_FN(get_latent_mode)(s4b_sampler* s, int32_t* mode);
 
 /* NUTS totals over all transitions since creation: {transitions, sum of treedepth__, sum of n_leapfrog__, divergent transitions}
  * (the per-draw values are columns 4-6 of the stan result; the totals let a caller that keeps no per-iteration output, keep_fits =

@@ -99,6 +99,8 @@ def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
 
+LATENT_MODES = {"exact": 0, "parallel": 1}      # bart_args latents -> s4b_set_latent_mode
+
 @dataclass
 class SamplerArgs:
     """The six argument objects of ``stan4bart_create`` (reference R/stan4bart_fit.R:42) as numpy/python."""
@@ -118,6 +120,7 @@ class SamplerArgs:
     split_probs: Optional[Sequence[float]] = None     # cgm(split.probs): one positive weight per BART predictor, or None (uniform)
     use_quantiles: bool = False                       # dbartsControl(useQuantiles): cut points from the distinct values
     k_hyper: Optional[tuple] = None                   # normal(k = chi(degreesOfFreedom, scale)): (df, scale) -> k is sampled; `k` is where it starts
+    latents: str = "exact"                            # probit latents: "exact" (R's stream, the reference's chain) or "parallel" (s4b_set_latent_mode 1)
     # stan data
     X: Optional[np.ndarray] = None          # n x K (already centred)
     y: Optional[np.ndarray] = None
@@ -259,6 +262,15 @@ class Sampler:
                                st.ctypes.data_as(c_uint32_p), C.byref(self._h))
         self._check(rc)
         self._keep.clear()
+        if a.latents not in LATENT_MODES:
+            self.free()
+            raise ValueError(f"latents must be one of {sorted(LATENT_MODES)}, not {a.latents!r}")
+        if a.latents != "exact":
+            try:
+                self.set_latent_mode(LATENT_MODES[a.latents])
+            except Exception:
+                self.free()
+                raise
         dims = (C.c_int64 * 5)()
         self._check(self._f("get_dims")(self._h, dims))
         self.num_pars, self.n, self.n_test, self.p, self.n_trees = (int(d) for d in dims)
@@ -291,6 +303,7 @@ class Sampler:
             "profile_sweep": [vp, i32, dp], "profile_leapfrog": [vp, i32, dp],
             "set_progress": [vp, PROGRESS, vp], "set_device_sharing": [vp, i32],
             "set_tree_path": [vp, i32], "get_tree_path": [vp, ip], "get_fused_stats": [vp, C.POINTER(i64)], "get_sweep_stats": [vp, C.POINTER(i64)], "get_sweep_busy": [vp, C.POINTER(i64)], "get_sweep_spec": [vp, C.POINTER(i64)], "set_test_hook": [vp, i32, i64], "set_hmc_mode": [vp, i32], "get_hmc_mode": [vp, ip],
+            "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip],
         }
         for name, argtypes in sig.items():
             fn = getattr(self._lib, self._pfx + name, None)
@@ -476,6 +489,21 @@ class Sampler:
         fn = getattr(self._lib, self._pfx + "get_hmc_mode", None)
         if fn is None:
             return 1          # (the oracle evaluates the likelihood per leapfrog, like the reference)
+        out = np.zeros(1, dtype=np.int32)
+        self._check(fn(self._h, _ip(out)))
+        return int(out[0])
+
+    def set_latent_mode(self, mode: int):
+        """How the probit latents are drawn: 0 exact (R's stream), 1 parallel (Philox, one thread per observation); before the first run."""
+        fn = getattr(self._lib, self._pfx + "set_latent_mode", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no set_latent_mode: it draws the probit latents from R's stream only")
+        self._check(fn(self._h, int(mode)))
+
+    def get_latent_mode(self) -> int:
+        fn = getattr(self._lib, self._pfx + "get_latent_mode", None)
+        if fn is None:
+            return 0
         out = np.zeros(1, dtype=np.int32)
         self._check(fn(self._h, _ip(out)))
         return int(out[0])

@@ -86,6 +86,8 @@ int S4B_FN(set_tree_path)(s4b_sampler* s, int32_t path) { S4B_NEED(s, "set_tree_
 int S4B_FN(get_tree_path)(s4b_sampler* s, int32_t out[2]) { S4B_NEED(s, "get_tree_path") S4B_TRY if (!out) throw std::invalid_argument("get_tree_path: NULL output pointer"); s->core.dev().get_tree_path(out); S4B_CATCH }
 int S4B_FN(set_hmc_mode)(s4b_sampler* s, int32_t mode) { S4B_NEED(s, "set_hmc_mode") S4B_TRY s->core.set_hmc_mode(mode); S4B_CATCH }
 int S4B_FN(get_hmc_mode)(s4b_sampler* s, int32_t* mode) { S4B_NEED(s, "get_hmc_mode") S4B_TRY if (!mode) throw std::invalid_argument("get_hmc_mode: NULL output pointer"); *mode = s->core.hmc_mode(); S4B_CATCH }
+int S4B_FN(set_latent_mode)(s4b_sampler* s, int32_t mode) { S4B_NEED(s, "set_latent_mode") S4B_TRY s->core.dev().bind(); s->core.set_latent_mode(mode); S4B_CATCH }
+int S4B_FN(get_latent_mode)(s4b_sampler* s, int32_t* mode) { S4B_NEED(s, "get_latent_mode") S4B_TRY if (!mode) throw std::invalid_argument("get_latent_mode: NULL output pointer"); *mode = s->core.latent_mode(); S4B_CATCH }
 int S4B_FN(get_fused_stats)(s4b_sampler* s, int64_t out[2]) { S4B_NEED(s, "get_fused_stats") S4B_TRY if (!out) throw std::invalid_argument("get_fused_stats: NULL output pointer"); s->core.dev().fused_stats(out); S4B_CATCH }
 int S4B_FN(get_sweep_stats)(s4b_sampler* s, int64_t out[2]) { S4B_NEED(s, "get_sweep_stats") S4B_TRY if (!out) throw std::invalid_argument("get_sweep_stats: NULL output pointer"); s->core.dev().sweep_stats(out); S4B_CATCH }
 int S4B_FN(get_sweep_spec)(s4b_sampler* s, int64_t out[4]) { S4B_NEED(s, "get_sweep_spec") S4B_TRY if (!out) throw std::invalid_argument("get_sweep_spec: NULL output pointer"); s->core.dev().sweep_spec(out); S4B_CATCH }

@@ -44,6 +44,7 @@ static __device__ unsigned long long g_dec[16];
                                                                       else { atomicAdd(&g_dec[i], (unsigned long long)wall_clock64() - g_dec[0]); atomicAdd(&g_dec[7 + (i)], 1ull); } } } while (0)
 #endif
 #include "sampler_core.hpp"
+#include "philox.hpp"
 
 namespace s4b {
 
@@ -1628,6 +1629,22 @@ __global__ __launch_bounds__(BLOCK) void k_latents_finish(BartArrays a, const do
     a.lat[i] = nl; a.R[i] = nl - fOld;
   }
 }
+// Latent mode 1: k_latents2 + k_latents_finish in one grid-stride pass, each latent drawn on its own from Philox4x32-10
+// (philox.hpp) with the counter {draw, observation, attempt} under the chain's key.  A latent depends on (key, draw, i, mean) only: not on the
+// launch geometry, the tree path or a sweep group.  Same arrays and stored conventions as k_latents_finish; R's stream is not touched.
+__global__ __launch_bounds__(BLOCK) void k_latents_par(BartArrays a, uint32_t k0, uint32_t k1, uint64_t draw) {
+  bool failed = false;
+  for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * BLOCK) {
+    const double fOld = a.lat[i] - a.R[i], offv = a.off[i], mean = fOld + offv;
+    const bool one = a.y[i] > 0.0;
+    double x;
+    failed |= !philox_trunc_normal(k0, k1, draw, (uint32_t)i, one ? 0.0 - mean : mean - 0.0, x);
+    const double z = one ? mean + x : mean - x;
+    const double nl = z - offv;
+    a.lat[i] = nl; a.R[i] = nl - fOld;
+  }
+  if (failed) atomicOr(a.errFlag, (int32_t)(S4B_ERR_INTERNAL | S4B_ERR_I_LATENT));
+}
 
 __global__ __launch_bounds__(BLOCK) void k_init_binary(BartArrays a) {   // latents 2y - 1, no tree fits yet
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -2718,7 +2735,18 @@ class DevHip {
       else hipLaunchKernelGGL((k_tree<true, false>), dim3(a_.grid), dim3(BLOCK), ldsTree_, stream_, a_, t);
     }
   }
+  // ---- probit latents: 0 = R's stream (the reference's draw, k_latents2 + k_latents_finish), 1 = k_latents_par under the chain's Philox key;
+  // its draw index is this host-side counter, advanced once per latent draw (launch_latents runs outside every captured graph)
+  int latMode_ = 0; uint64_t latKey_ = 0, latDraw_ = 0;
+  void set_latent_mode(int mode, uint64_t key) { latMode_ = mode; latKey_ = key; }
+  void latent_state(uint64_t out[2]) const { out[0] = latKey_; out[1] = latDraw_; }
+  void set_latent_state(uint64_t key, uint64_t draw) { latKey_ = key; latDraw_ = draw; }
   void launch_latents() {
+    if (latMode_ == 1) {
+      hipLaunchKernelGGL(k_latents_par, dim3(gridN_), dim3(BLOCK), 0, stream_, a_, (uint32_t)latKey_, (uint32_t)(latKey_ >> 32), latDraw_);
+      ++latDraw_; ++launches_;
+      return;
+    }
     if (latX_) {
       hipLaunchKernelGGL(k_latents2, dim3(1), dim3(LB2), lat2_lds_bytes(), stream_, a_, latX_);
       hipLaunchKernelGGL(k_latents_finish, dim3(gridN_), dim3(BLOCK), 0, stream_, a_, (const double*)latX_);

@@ -19,6 +19,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -50,6 +51,10 @@ struct DevInit {
   const double* w = nullptr; const int32_t* v = nullptr; const int32_t* u = nullptr; int64_t nnz = 0;
   int32_t traceCap = 0;
 };
+
+// does the device layer draw the probit latents in parallel (latent mode 1: set_latent_mode, latent_state, set_latent_state)?
+template <class D, class = void> struct has_latent_mode : std::false_type {};
+template <class D> struct has_latent_mode<D, std::void_t<decltype(&D::set_latent_mode)>> : std::true_type {};
 
 template <class Dev>
 class SamplerCore {
@@ -150,6 +155,7 @@ class SamplerCore {
     if (cc->offset) { userOffset_.assign(cc->offset, cc->offset + n_); hasUserOffset_ = true; }
     rng_.mti = (int32_t)rstate[0]; rng_.pad = 0;
     std::memcpy(rng_.mt, rstate + 1, 624 * sizeof(uint32_t));
+    latKey_ = latent_key(rstate, sc->seed);
 
     // ---- Stan spec + host copies of the design (the reference copies them too: stan_sampler.cpp:197-249)
     StanSpec sp;
@@ -258,6 +264,7 @@ class SamplerCore {
   void run(int numIter, bool isWarmup, int resultsType, s4b_results* out) {
     live();
     if (numIter < 1) throw std::invalid_argument("num_iter must be >= 1");
+    ran_ = true;
     dev_.reset_fused_scales();     // (history-independent at every call boundary: see DevHip::reset_fused_scales)
     const bool doStan = resultsType == 0 || resultsType == 2, doBart = resultsType == 0 || resultsType == 1;
     const int numPars = (int)row_.size();
@@ -489,13 +496,14 @@ class SamplerCore {
       }
       treeBytes += 8 + nodes[(size_t)t].size() * 4 + leafMu[(size_t)t].size() * 8;
     }
-    const size_t need = sizeof(s4b_state_header) + (size_t)(4 * D + 6 + 7) * 8 + (8 + 2 + 626) * 4 + 4 * 8 + (size_t)(binary_ ? 3 : 2) * n_ * 8 + treeBytes;
+    const size_t need = sizeof(s4b_state_header) + (size_t)(4 * D + 6 + 7) * 8 + (8 + 2 + 626) * 4 + 4 * 8 + (size_t)(binary_ ? 3 : 2) * n_ * 8 + treeBytes + (latMode_ ? 16 : 0);
     if (!buf || cap < (int64_t)need) return (int64_t)need;
     unsigned char* o = (unsigned char*)buf;
     auto put = [&](const void* src, size_t k) { if (k) std::memcpy(o, src, k); o += k; };
     s4b_state_header hd; std::memset(&hd, 0, sizeof(hd));
     hd.magic = S4B_STATE_MAGIC; hd.version = 1; hd.n = (int64_t)n_; hd.n_trees = T_; hd.num_unconstrained = D; hd.is_binary = binary_ ? 1 : 0; hd.p = P_;
     if (kModeled_) { const double kk = dev_.k_current(); std::memcpy(&hd.reserved[0], &kk, 8); }
+    hd.reserved[1] = latMode_;
     put(&hd, sizeof(hd));
     Nuts::State ns; nuts_->get_state(ns);
     put(ns.q.data(), (size_t)D * 8); put(ns.inv_metric.data(), (size_t)D * 8); put(ns.wm.data(), (size_t)D * 8); put(ns.wm2.data(), (size_t)D * 8);
@@ -520,6 +528,7 @@ class SamplerCore {
       const int32_t cnt[2] = {(int32_t)(nodes[(size_t)t].size() / 2), (int32_t)leafMu[(size_t)t].size()};
       put(cnt, sizeof(cnt)); put(nodes[(size_t)t].data(), nodes[(size_t)t].size() * 4); put(leafMu[(size_t)t].data(), leafMu[(size_t)t].size() * 8);
     }
+    if (latMode_) { uint64_t ls[2]; dev_latent_state(ls); put(ls, sizeof(ls)); }
     return (int64_t)need;
   }
   void set_state(const void* buf, int64_t size) {
@@ -534,6 +543,9 @@ class SamplerCore {
     if (hd.version != 1u) throw std::invalid_argument("sampler state: unknown version");
     if (hd.n != (int64_t)n_ || hd.n_trees != T_ || hd.num_unconstrained != D || (hd.is_binary != 0) != binary_ || hd.p != P_)
       throw std::invalid_argument("sampler state: dimensions do not match this sampler");
+    if (hd.reserved[1] != (int64_t)latMode_)       // (symmetric, like the k flag below: neither mode's chain is continued by the other's draw)
+      throw std::invalid_argument("sampler state: it was written in latent mode " + std::to_string(hd.reserved[1]) + ", this sampler is in latent mode " +
+                                  std::to_string(latMode_) + " (set_latent_mode before set_state)");
     Nuts::State ns;
     ns.q.resize((size_t)D); ns.inv_metric.resize((size_t)D); ns.wm.resize((size_t)D); ns.wm2.resize((size_t)D);
     r.get(ns.q.data(), (size_t)D * 8); r.get(ns.inv_metric.data(), (size_t)D * 8); r.get(ns.wm.data(), (size_t)D * 8); r.get(ns.wm2.data(), (size_t)D * 8);
@@ -578,6 +590,8 @@ class SamplerCore {
       if (!open.empty() || leaf != cnt[1]) throw std::invalid_argument("sampler state: malformed tree");
       h.hwm[(size_t)t] = cnt[0];
     }
+    uint64_t ls[2] = {0, 0};
+    if (latMode_) { ls[0] = r.u64(); ls[1] = r.u64(); }
     // nothing non-finite reaches the device or the adaptation state (the blob may come from a file or another process)
     {
       auto finite = [](const double* x, size_t k) { for (size_t i = 0; i < k; ++i) if (!std::isfinite(x[i])) return false; return true; };
@@ -595,6 +609,7 @@ class SamplerCore {
     } else if (kState != 0.0) throw std::invalid_argument("sampler state: it carries the value of a modeled k, this sampler's k is fixed");
     // ---- commit
     if (kModeled_) dev_.set_k(kState);
+    if (latMode_) dev_set_latent_state(ls);
     nuts_->set_state(ns);
     dev_.reset_fused_scales();
     nuts_->current_row(row_.data());
@@ -623,6 +638,18 @@ class SamplerCore {
     if (mode != 0 && mode != 1) throw std::invalid_argument("hmc_mode must be 0 (sufficient statistics) or 1 (one device evaluation per leapfrog)");
     if (mode == 0 && !haveGram_) throw std::invalid_argument("this sampler was created with hmc_mode 1: it has no Gram matrix to evaluate from sufficient statistics");
     hmcMode_ = mode;
+  }
+  // latent mode (s4b_set_latent_mode): 0 = the reference's draw from R's stream, 1 = parallel draw under the chain's Philox key
+  static constexpr bool kLatentMode = has_latent_mode<Dev>::value;
+  int latent_mode() const { live(); return latMode_; }
+  void set_latent_mode(int mode) {
+    live();
+    if (mode != 0 && mode != 1) throw std::invalid_argument("latent mode must be 0 (exact: R's stream, the reference's draw) or 1 (parallel: counter-based, one thread per observation)");
+    if (mode == latMode_) return;
+    if (mode == 1 && !binary_) throw std::invalid_argument("latent mode 1 (parallel) draws probit latents: this sampler's response is continuous");
+    if (ran_) throw std::invalid_argument("the latent mode is set before the first run");
+    if constexpr (kLatentMode) { dev_.set_latent_mode(mode, latKey_); latMode_ = mode; }
+    else throw std::invalid_argument("this device layer has no parallel latent draw: latent mode 1 needs the HIP device layer");
   }
   int64_t get_trace(int64_t cap, int32_t* out) { live(); return dev_.get_trace(cap, out); }
   void leaf_assignment(int t, int32_t* out) {
@@ -709,6 +736,16 @@ class SamplerCore {
     }
     dev_.sweep_and_stan_inputs(thin_, stan_mode(), wantTrain, cX_.data(), cZ_.data(), &s0_, train);
   }
+  // The Philox key of latent mode 1: a hash of the generator state and Stan seed the chain was created with — nothing is drawn from R's stream,
+  // chains with different seeds get different keys
+  static uint64_t latent_key(const uint32_t* rstate, uint32_t seed) {
+    auto mix = [](uint64_t z) { z += 0x9E3779B97F4A7C15ull; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return z ^ (z >> 31); };
+    uint64_t h = mix(seed);
+    for (int i = 0; i < 625; ++i) h = mix(h ^ rstate[i]);
+    return h;
+  }
+  void dev_latent_state(uint64_t ls[2]) { if constexpr (kLatentMode) dev_.latent_state(ls); else ls[0] = ls[1] = 0; }
+  void dev_set_latent_state(const uint64_t ls[2]) { if constexpr (kLatentMode) dev_.set_latent_state(ls[0], ls[1]); }
   static constexpr uint32_t STATE_MAGIC = 0x54423453u;   // "S4BT"
   struct Reader {
     const unsigned char* p; size_t n, pos; const char* what = "exported BART state: truncated";
@@ -931,6 +968,7 @@ class SamplerCore {
   void check_device() {
     int32_t e = dev_.error_flags();
     if (e & S4B_ERR_NODE_CAPACITY) throw std::runtime_error("a tree outgrew node_capacity; re-create the sampler with a larger bart_control.node_capacity");
+    if (e & S4B_ERR_I_LATENT) throw std::runtime_error("parallel latents: no proposal was accepted for an observation (a non-finite mean; device error word " + std::to_string(e) + ")");
     if (e & S4B_ERR_INTERNAL) throw std::runtime_error("internal error: a hand-shake of the control kernel timed out (device error word " + std::to_string(e) + ")");
     if (e & S4B_ERR_TRACE_OVERFLOW) throw std::runtime_error("trace buffer overflow: call get_trace more often");
   }
@@ -947,6 +985,7 @@ class SamplerCore {
   ModelView hostModelView_;
   std::unique_ptr<HostModel> model_; std::unique_ptr<Nuts> nuts_;
   bool keepTrees_ = false, kModeled_ = false; double kFixed_ = 2.0;
+  int latMode_ = 0; uint64_t latKey_ = 0; bool ran_ = false;
   std::vector<PackedNode> keptNodes_; std::vector<int64_t> keptTreeStart_; std::vector<double> keptScale_;
   std::vector<double> row_, cX_, cZ_, gram_, gramDense_; int gramLd_ = 0; std::vector<int> gramPtr_, gramCol_; double s0_ = 0, sigma_ = 1;
   long treeUpdates_ = 0;

@@ -309,13 +309,18 @@ def make_sampler_args(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_tes
     if refresh is None:
         refresh = max(iter // 10, 1)
     off_types = ["default", "fixef", "ranef", "bart", "parametric"]
+    latents = bart_args.get("latents", "exact")
+    if latents not in ("exact", "parallel"):
+        raise ValueError(f"bart_args['latents'] must be 'exact' or 'parallel', not {latents!r}")
+    if latents == "parallel" and not is_binary:
+        raise ValueError("bart_args['latents'] = 'parallel' draws probit latents: it needs a binary response (family='binomial')")
     return SamplerArgs(
         x_bart=np.asarray(x_bart, dtype=np.float64), x_test=x_test,
         n_trees=int(bart_args.get("n.trees", 75)), n_cuts=bart_args.get("n.cuts", 100), n_thin=skip_bart,
         base=float(bart_args.get("base", 0.95)), power=float(bart_args.get("power", 2.0)),
         k=_k_prior(bart_args.get("k", 2.0))[0], k_hyper=_k_prior(bart_args.get("k", 2.0))[1], keep_trees=bool(bart_args.get("keepTrees", False)),
         split_probs=_split_probs(bart_args.get("split.probs"), np.asarray(x_bart).shape[1], bart_args.get("predictor.names")),
-        use_quantiles=bool(bart_args.get("useQuantiles", False)),
+        use_quantiles=bool(bart_args.get("useQuantiles", False)), latents=latents,
         node_scale=3.0 if is_binary else 0.5,
         X=Xc, y=y, weights=weights, is_binary=is_binary, prior_dist=prior_dist, prior_dist_for_aux=0 if is_binary else 3,
         prior_scale=prior_scale, prior_mean=prior_mean, prior_df=prior_df, num_normals=num_normals, **hs_args,

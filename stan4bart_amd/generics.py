@@ -74,6 +74,7 @@ class Stan4bartFit:
     weights: Optional[np.ndarray] = None    # observation weights of the training sample
     k: Optional[np.ndarray] = None          # [iterations, chains] draws of a modeled end-node sensitivity k (bart_args k = chi(...)), else None
     batch_stats: Optional[dict] = None      # batch_chains=True: the sweep groups' counters summed over the thread batches, else None
+    latents: str = "exact"                  # how the probit latents were drawn (bart_args latents): "exact" or "parallel"
 
     # ------------------------------------------------------------------ helpers
     def _get(self, name: str, include_warmup, only_warmup):
@@ -520,4 +521,5 @@ def stan4bart(y, x_bart, X=None, groups: Sequence[GroupTerm] = (), x_bart_test=N
         terms=terms, terms_test=terms_test, offset=None if offset is None else np.asarray(offset, dtype=np.float64),
         offset_test=None if offset_test is None else np.asarray(offset_test, dtype=np.float64), offset_type=offset_type,
         range_bart=np.stack([r["range.bart"] for r in results], axis=1), samplers=samplers, callback=smp["callback"],
-        weights=None if kw.get("weights") is None else np.asarray(kw["weights"], dtype=np.float64), k=smp["k"], batch_stats=batch_stats)
+        weights=None if kw.get("weights") is None else np.asarray(kw["weights"], dtype=np.float64), k=smp["k"], batch_stats=batch_stats,
+        latents=args.latents)

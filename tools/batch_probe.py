@@ -3,7 +3,7 @@
 treatment counterfactual, 75 trees, n = 747) and a Gaussian fit with random effects at n = 4 096 (the largest solo sweep).  The batched
 and unbatched runs alternate, in one process; every run builds fresh samplers and times warmup + sampling after one untimed iteration.
 
-    python tools/batch_probe.py [--iter 60] [--reps 2] [--out profiles/batch_probe.jsonl]
+    python tools/batch_probe.py [--iter 60] [--reps 2] [--out profiles/batch_probe.jsonl] [--latents parallel]
 """
 import argparse
 import copy
@@ -78,6 +78,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--shapes", default="ihdp,gauss", help="comma-separated prefixes of the shapes to run")
     ap.add_argument("--batched-only", action="store_true", help="only the batched runs (a kernel trace of the batched launches)")
+    ap.add_argument("--latents", choices=("exact", "parallel"), default="exact", help="probit latents of the binary shape (bart_args latents)")
     o = ap.parse_args()
     from stan4bart_amd._lib import load_library
     lib = load_library()
@@ -85,6 +86,8 @@ def main():
     for name, args in shapes(o.iter).items():
         if not any(name.startswith(p) for p in o.shapes.split(",")):
             continue
+        if args.is_binary:
+            args.latents = o.latents
         for C in [int(c) for c in o.chains.split(",")]:
             rates = {False: [], True: []}
             stats = None
@@ -94,7 +97,7 @@ def main():
                     rates[batched].append(r)
                     stats = st if batched else stats
             ub = max(rates[False]) if rates[False] else None
-            rec = dict(shape=name, chains=C, iter=o.iter, unbatched_it_s=ub, batched_it_s=max(rates[True]),
+            rec = dict(shape=name, latents=args.latents, chains=C, iter=o.iter, unbatched_it_s=ub, batched_it_s=max(rates[True]),
                        speedup=max(rates[True]) / ub if ub else None, all_unbatched=rates[False], all_batched=rates[True], group_stats=stats)
             print(json.dumps(rec), flush=True)
             if out:

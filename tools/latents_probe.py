@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Cost of the probit latent draws per observation on the GPU box: a binary-response chain with few trees, timed per Gibbs
-iteration with the table kernel (default) and with S4B_LATENTS=1 (serial-bookkeeping kernel) — run it once per setting.
-    python tools/latents_probe.py --n 1000000"""
+iteration with the table kernel (default), with S4B_LATENTS=1 (serial-bookkeeping kernel) or with --latents parallel (k_latents_par,
+latent mode 1) — run it once per setting.
+    python tools/latents_probe.py --n 1000000 [--latents parallel]"""
 import argparse
 import os
 import sys
@@ -17,6 +18,7 @@ def main():
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--trees", type=int, default=10)
     ap.add_argument("--iters", type=int, default=6)
+    ap.add_argument("--latents", choices=("exact", "parallel"), default="exact")
     a = ap.parse_args()
     from stan4bart_amd import RRng, make_sampler_args
     from stan4bart_amd._lib import load_library
@@ -27,7 +29,7 @@ def main():
     eta = 2.0 * np.sin(np.pi * xb[:, 0] * xb[:, 1]) + 2.0 * (xb[:, 2] - 0.5) + 1.5 * (x4 - 0.5)
     y = (eta + g.standard_normal(a.n) > 1.0).astype(np.float64)
     args = make_sampler_args(y, xb, X=x4.reshape(-1, 1), groups=[], family="binomial", iter=2 * a.iters, warmup=a.iters, keep_fits=False,
-                             bart_args={"n.trees": a.trees})
+                             bart_args={"n.trees": a.trees, "latents": a.latents})
     rng = RRng(77)
     args.seed = int(rng.sample_int(2147483647, 1)[0])
     s = Sampler(load_library(), "s4b_", args, rng.state)
@@ -37,7 +39,7 @@ def main():
     dt = (time.perf_counter() - t0) / a.iters
     st = s.get_r_rng_state()
     s.free()
-    print(f"n={a.n} trees={a.trees}: {dt * 1e3:.3f} ms per BART iteration = {dt / a.n * 1e6:.4f} us per observation (sweep included); mean(y)={y.mean():.3f}; rng checksum {int(st.astype(np.uint64).sum())}")
+    print(f"n={a.n} trees={a.trees} latents={a.latents}: {dt * 1e3:.3f} ms per BART iteration = {dt / a.n * 1e6:.4f} us per observation (sweep included); mean(y)={y.mean():.3f}; rng checksum {int(st.astype(np.uint64).sum())}")
 
 
 if __name__ == "__main__":
