@@ -1847,12 +1847,17 @@ __global__ __launch_bounds__(SBLOCK) void k_stan_fused(BartArrays a, StanArrays 
       if (f.mode >= 2) o.uo = a.userOffset[i];
     }
     if (a.wts) o.wt = a.wts[i];
-    if (q) {
-      if (fixedRows) {
-        const size_t b = (size_t)i * (size_t)zf;
+    // (every field of the Z part is defined on both paths: with the other path's fields left unset the compiler kept two ints of the struct in
+    // private memory, 20 bytes of scratch per lane and a store + two loads per observation in all eight instantiations)
+    if (q && fixedRows) {
+      const size_t b = (size_t)i * (size_t)zf;
 #pragma unroll
-        for (int z = 0; z < S_ZMAX; ++z) if (z < zf) { o.zw[z] = s.w[b + z]; o.zv[z] = s.v[b + z]; }
-      } else { o.r0 = s.u[i]; o.r1 = s.u[i + 1]; }
+      for (int z = 0; z < S_ZMAX; ++z) { const bool on = z < zf; o.zw[z] = on ? s.w[b + z] : 0.0; o.zv[z] = on ? s.v[b + z] : 0; }
+      o.r0 = 0; o.r1 = 0;
+    } else {
+#pragma unroll
+      for (int z = 0; z < S_ZMAX; ++z) { o.zw[z] = 0.0; o.zv[z] = 0; }
+      o.r0 = q ? s.u[i] : 0; o.r1 = q ? s.u[i + 1] : 0;
     }
   };
   auto use = [&](int64_t i, const Obs& o) {
