@@ -67,7 +67,7 @@ class SamplerCore {
     if (r.u32() != 1u) throw std::invalid_argument("exported BART state: unknown version");
     P_ = (int)r.u32(); T_ = (int)r.u32(); binary_ = r.u32() != 0;
     const uint64_t S = r.u64(), numNodes = r.u64();
-    if (P_ < 1 || T_ < 1) throw std::invalid_argument("exported BART state: bad dimensions");
+    if (P_ < 1 || P_ > 32767 || T_ < 1) throw std::invalid_argument("exported BART state: bad dimensions");
     numCuts_.resize((size_t)P_); r.get(numCuts_.data(), (size_t)P_ * 4);
     cuts_.resize((size_t)P_);
     for (int j = 0; j < P_; ++j) { if (numCuts_[(size_t)j] < 0 || numCuts_[(size_t)j] > 65534) throw std::invalid_argument("exported BART state: bad cut count");
@@ -130,6 +130,8 @@ class SamplerCore {
     if (bc->interface_version != S4B_INTERFACE_VERSION) throw std::invalid_argument("s4b_bart_control.interface_version must be S4B_INTERFACE_VERSION (the caller was compiled against another revision of stan4bart_amd.h)");
     if (bd->n != sd->N) throw std::invalid_argument("bart data n != stan data N");
     if (bd->n < 1 || bd->p < 1) throw std::invalid_argument("bart data must have n >= 1, p >= 1");
+    // (a rule stores its predictor as int16_t — tree arrays, PackedNode::var, with negative values for leaves and free slots: a larger index would wrap into those)
+    if (bd->p > 32767) throw std::invalid_argument("bart data: at most 32767 predictors (a rule stores its predictor as int16_t)");
     if (bc->n_trees < 1) throw std::invalid_argument("n_trees must be >= 1");
     if (!(cc->sigma_init > 0)) throw std::invalid_argument("sigma_init must be > 0");
     if ((cc->is_binary != 0) != (sd->is_binary != 0)) throw std::invalid_argument("common_control.is_binary and stan_data.is_binary disagree");
