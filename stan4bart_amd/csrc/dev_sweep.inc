@@ -1,5 +1,5 @@
-// k_sweep: the PERSISTENT tree sweep — ONE launch per sweep (included by dev_hip.hip inside namespace s4b, after dev_step.inc; the
-// kernel body is compiled in the translation unit dev_sweep.hip only).
+// k_sweep: the PERSISTENT tree sweep — ONE launch per sweep (the device-only helpers and the kernel bodies of the translation unit
+// dev_sweep.hip, which includes this file once, after the shared headers and dev_sweep_api.hpp).
 //
 // k_step pays, per tree, one kernel boundary (1.7 us), a cold first touch of everything another XCD wrote (3 us: partials, scratch
 // set, proposal images, generator) and 22 B per observation of residual / leaf-plane traffic, and its O(N) pass (4.5 us) starts only
@@ -25,7 +25,7 @@
 //   * per tree a thread reads 2 B (leaf id) + 2-6 B (predictor columns) per observation and writes 2 B under an accepted move,
 //     instead of 22 B;
 //   * the only words that cross workgroups are the bin partials: per bin two 64-bit fixed-point words ADDED into 8 copies with
-//     agent-scope integer atomics (xc_publish, dev_step.inc) — order-free, hence deterministic, every workgroup reads the same
+//     agent-scope integer atomics (xc_publish, dev_step_shared.hpp) — order-free, hence deterministic, every workgroup reads the same
 //     totals — polled by one wave per workgroup (8 x 2 nb words); profiles/r04_sweep_probe.txt: 2.1 us (4 bins) .. 3.3 us (8 bins)
 //     against 4.8 .. 6.5 us for an all-to-all gather of per-workgroup partials and ~5 us for k_step's boundary + cold reduce.
 //   * SPECULATION (round 5): the outcome "the move of tree t-1 is not accepted and image 0 of tree t is its proposal" (98 % of the steps
@@ -39,11 +39,10 @@
 // What does not fit (a tree beyond the 64 node slots of the wave-register control path) ends the launch early in exactly the state
 // k_step expects at the next launch (residual, partials, scratch set, generator slot written back, the sequential global-memory
 // control step run by the last workgroup); the host finishes that sweep with k_step launches (status word).
-#if defined(S4B_SWEEP_TIMING) || defined(S4B_SWEEP_WGT) || defined(S4B_SWEEP_WGD)
+namespace s4b {
+#ifdef S4B_SWEEP_WG
 // per-workgroup stamps of the exchange (`-DS4B_SWEEP_WGT` alone: nothing else is timed, every workgroup carries the same four atomics per step)
-#define S4B_SWEEP_WG 1
 #define SW_W(i) do { if (lane == 0 && t > 0 && t < T && (int)SW_BX < 256) atomicAdd(&g_wg[SW_BX * 16 + (i)], (unsigned long long)wall_clock64() - (unsigned long long)F.t0[t & 3]); } while (0)
-#ifdef S4B_SWEEP_TU
 __device__ unsigned long long g_pubMax[8], g_pubMin[8];     // wall clock of the last / first speculative publish of step t (slot t & 7)
 // per workgroup: [0] sum of (speculative publish - totals seen) [1] steps [2] sum of the wall clock when the totals were seen [3] steps
 //                [4] sum of (totals of step t+1 seen - last speculative publish of step t) [5] steps [6] sum of (last - first publish) [7] -
@@ -67,10 +66,6 @@ void sweep_wd_fetch(unsigned long long* out) {   // (reads and clears)
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wd), sizeof(g_wd));
   static unsigned long long z[256 * 64]; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wd), z, sizeof(z));
 }
-#else
-void sweep_wg_fetch(unsigned long long* out);
-void sweep_wd_fetch(unsigned long long* out);
-#endif
 #endif
 #ifndef S4B_SWEEP_WG
 #define SW_W(i)
@@ -106,7 +101,6 @@ void sweep_wd_fetch(unsigned long long* out);
 //   image waves: [24..27] propose() time by move type, [36..39] counts, [62] without a valid move, [63] start of the drawing step -> propose();
 //     drawings that took > 8 us: [15] count  [13] generator copied  [14] wait for the staged tree  [29] tree loaded + generator advanced  [34] propose()
 //     [70] image stored; all drawings: [64] cache invalid  [65] generator block renewed  [66..68] tree loaded / cache / generator opened  [69] count
-#ifdef S4B_SWEEP_TU
 __device__ unsigned long long g_sw[128];
 void sweep_timing_fetch(unsigned long long* out) {   // (reads and clears)
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sw), sizeof(g_sw));
@@ -116,10 +110,6 @@ void sweep_decide_fetch(unsigned long long* out) {   // (reads and clears)
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dec), sizeof(g_dec));
   unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_dec), z, sizeof(z));
 }
-#else
-void sweep_timing_fetch(unsigned long long* out);
-void sweep_decide_fetch(unsigned long long* out);
-#endif
 #define SW_T(i) do { if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 0 && t < T) atomicAdd(&F.tacc[i], (unsigned long long)(wall_clock64() - tStep)); } while (0)
 #define SW_MARK() tStep = wall_clock64()
 #define SW_AP(i) do { if ((int)SW_BX == SW_TIMED_WG && lane == 0 && t > 1 && t < T) atomicAdd(&F.tacc[i], (unsigned long long)(wall_clock64() - F.t0[(t - 1) & 3])); } while (0)
@@ -135,26 +125,7 @@ void sweep_decide_fetch(unsigned long long* out);
 #define SW_A(i)
 #define SW_AP(i)
 #endif
-constexpr int SW_NC = 64;            // node slots of the wave-register control path = row length of the on-chip tables
-constexpr int SW_PW = 4;             // pass waves (4..7): one per SIMD
-constexpr int SW_PT = SW_PW * 64;    // pass threads per workgroup
-constexpr int SW_PF = 4;             // quads per pass thread (16 observations), all of them in registers for the whole sweep
-constexpr unsigned long long SW_ROLL_GO = 1ull, SW_ROLL_BUSY = 2ull;
 constexpr long long SW_ROLL_TICKS = 20000;   // 200 us of the 100 MHz wall clock: a launch on a free device has all its workgroups running within a few microseconds
-constexpr int XC_ROLL_WORDS = 8;     // words behind each exchange ring: [0] tickets of the roll call, [1] its decision
-constexpr int SW_SETS = 6;           // statistics-half table sets: 0 wave 0's own proposal, 1 + sw_slot(tree, c) image c of the tree
-constexpr int SW_SLOTS = 5;          // image slots: image 0 of tree t in slot t % 3 (it is drawn one step AHEAD), image 1 in slot 3 + (t & 1)
-constexpr int SW_STAGES = 3;         // staged trees: tree t in stage t % 3 (staged two steps before it is decided)
-// LINEAR statistics (round 6; see "LINEARITY" at the pass waves): the O(N) statistics pass of tree t+1 runs one step AHEAD, over the residual with
-// tree t still missing, and gathers beside the bin sums the integer CONTINGENCY counts (leaf of tree t) x (bin of tree t+1); when the leaf values
-// of tree t arrive, the exchange wave turns both into the workgroup's statistics with (leaves x bins) multiply-adds and publishes them itself.
-// Built, parity-green against the oracle over the whole GPU suite, measured — and NOT the default (gate of VERDICT r05 item 1: "if the step does not drop by
-// >= 1.2 us, record and stop"): 9.0 us per tree update in the benchmark's stationary chain against 8.45 for the statistics on the chain (profiles/r06_linear_gate.txt;
-// DESIGN.md 8, round 6: the pass waves' work per step — route 2.0 + ahead pass 3.0 + fold — and one proposal drawing per step on wave 1 become the bound once the
-// exchange no longer is).  `make linear` builds libs4b_linear.so; tests/test_gpu_linear.py keeps it under the oracle.
-#ifndef S4B_LINEAR
-#define S4B_LINEAR 0
-#endif
 #ifndef S4B_LFAHEAD
 #define S4B_LFAHEAD 0      // 1: the leaf ids of a step requested during the step before, in front of the wait for wave 3's leaf values (`make lfahead`).  Measured SLOWER, round 6:
                            // 1 756 - 1 762 against 1 698 - 1 707 us per sweep, A/B/A/B/A/B — packing them is their first use, and the wait for the memory counter in front of it
@@ -164,21 +135,13 @@ constexpr int SW_STAGES = 3;         // staged trees: tree t in stage t % 3 (sta
 #define S4B_PREBITS 0      // 1: the bin bits and bin counts of a step's statistics gathered behind the routing, off the chain of the step (needs S4B_WAVERED; `make prebits`).  Measured
                            // SLOWER, round 6: 1 761 - 1 776 against 1 716 - 1 725 us per sweep, same box A/B/A/B — the window behind the routing is not idle enough for 0.7 us more
 #endif
-#ifndef S4B_WAVERED
-#define S4B_WAVERED 1      // the statistics' reduction: 1 per pass wave in registers, the last wave to arrive publishes (round 6); 0 the block reduction through LDS of round 5
-#endif
 #ifndef S4B_X1
 #define S4B_X1 0      // (1: the arrival behind the ahead pass waits for the wave's LDS counter only — measured: the chain then differs from the oracle's in one run of four; 0: a release fence)
 #endif
 #ifndef S4B_X2
 #define S4B_X2 1
 #endif
-constexpr int SW_CC = 4;                               // copies of every contingency count: lane & 3 picks one (lanes of a wave with the same key spread over four banks)
-constexpr int SW_CT_WORDS = SW_NC * 8 * SW_CC + 16;    // counts [node of tree t][bin of tree t+1][copy] + a row of dummies for the observations that are in no bin
-struct SweepArgs { unsigned long long* xbuf; int32_t* status; unsigned long long* xnext; double wScale, wUnscale; };   // (wScale / wUnscale: observation weights, k_sweep_w — a power of two and its inverse)   // exchange ring [XC_RING][XC_COPIES][XC_WORDS]; host-visible status word; the ring of the NEXT launch (cleared by this one)
 
-// tree t as the main arrays hold it, staged in LDS one step before a wave proposes for it
-struct __attribute__((aligned(16))) TreeStage { int16_t row[TF_COUNT][SW_NC]; double mu[SW_NC]; int32_t cnt[SW_NC]; int32_t sc[TI_COUNT]; int32_t pad0[2]; double logPi; };
 struct SweepModel { double pg[64], lpg[64], l1pg[64], li0[64], li1[64]; int nc0[64], nc1[64]; double sigma; };
 struct SweepShared {
   // the decided tree t-1, for the pass (written by wave 0 before tablesReady = t)
@@ -219,15 +182,9 @@ struct SweepShared {
   double totS[64], totC[64];
   MTState rngB[2];
 };
-constexpr int SW_RED_ROW = SW_PT + 8;   // per-thread partials of one bin, one row per bin (padded: the rows of the 8 bins start 16 banks apart)
 struct SweepLds { NodeS* S; NodeP* SP; NodeA* A; uint8_t* Ain; uint8_t* b2n; double* redS; int* redN; unsigned char* img; TreeStage* stage;
                   NodeS* SA; NodeP* AP;      // SA / AP: apply-half routing tables of the streaming variant (the decided tree t-1 as proposed: node -> itself, rules)
                   unsigned* ctab; double* preS; int* preC; NodeA* zeroA; double* dtab; };     // dtab: old - new leaf value of the tree before, by parity of the step (the ahead pass folds through it)   // linear statistics: contingency counts and pre-sums by parity of the tree, a leaf-value table of zeros
-__host__ __device__ static inline size_t stage_bytes() { return (sizeof(TreeStage) + 15) / 16 * 16; }
-__host__ __device__ static inline size_t sweep_lds_bytes() {
-  return (size_t)SW_SETS * SW_NC * 24 + (size_t)2 * SW_NC * 16 + 64 + 64 + (size_t)8 * SW_RED_ROW * 12 + SW_SLOTS * cand_bytes(SW_NC) + SW_STAGES * stage_bytes() + (size_t)SW_NC * 24 +
-         (size_t)2 * SW_CT_WORDS * 4 + (size_t)2 * SW_PW * 8 * 8 + (size_t)2 * 8 * 4 + (size_t)SW_NC * 16 + (size_t)2 * SW_NC * 8;
-}
 __device__ __forceinline__ SweepLds carve_sweep(unsigned char* base) {
   SweepLds L;
   L.S = (NodeS*)base; base += (size_t)SW_SETS * SW_NC * 16;
@@ -337,14 +294,6 @@ __device__ __forceinline__ void pass_barrier(PassBar& b) {
   const BartArrays& a = *(const BartArrays*)kp_;                                                                             \
   const SweepArgs& x = *(const SweepArgs*)(kp_ + (sizeof(BartArrays) + 7) / 8 * 8); (void)x; (void)a
 #include "sweep_batch.inc"
-#ifndef S4B_SWEEP_TU
-__global__ __launch_bounds__(FBLOCK) void k_sweep(BartArrays aKern, SweepArgs xKern);
-__global__ __launch_bounds__(FBLOCK) void k_sweep_stream(BartArrays aKern, SweepArgs xKern);
-__global__ __launch_bounds__(FBLOCK) void k_sweep_few(BartArrays aKern, SweepArgs xKern);
-__global__ __launch_bounds__(FBLOCK) void k_sweep_sp(BartArrays aKern, SweepArgs xKern);
-__global__ __launch_bounds__(FBLOCK) void k_sweep_few_sp(BartArrays aKern, SweepArgs xKern);
-__global__ __launch_bounds__(FBLOCK) void k_sweep_w(BartArrays aKern, SweepArgs xKern);
-#else
 // per-observation state of a pass thread: 4 quads.  Packed fields hold one byte per observation of the quad.
 // (round 6: the leaf ids too — three trees are in flight per thread since the statistics run a step ahead; node ids of the wave path are < 64)
 typedef unsigned lfq_t;
@@ -1045,7 +994,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
   __shared__ ControlShared S;
   __shared__ SweepShared F;
   __shared__ SweepModel M;
-  __shared__ double spTab[SPL ? SP_TAB : 1];      // (cgm(split.probs): WaveModelT<true>, dev_hip.hip)
+  __shared__ double spTab[SPL ? SP_TAB : 1];      // (cgm(split.probs): WaveModelT<true>, dev_control.hpp)
   __shared__ __attribute__((aligned(16))) double wLds[WT ? SW_PT * SW_PF * 4 : 2];      // (observation weights of the workgroup's observations: sweep_stats<.., WT>)
   constexpr int NBX = WT ? 2 : 1;      // "bins" a step exchanges per bin of its statistics (the sums of the weights travel as bins of their own)
   static_assert(!(WT && STREAM), "no weighted streaming sweep"); static_assert(!(BATCH && STREAM), "the streaming sweep is never solo");
@@ -2715,7 +2664,7 @@ __global__ __launch_bounds__(FBLOCK) void k_sweep(BartArrays aKern, SweepArgs xK
 // (the same launch for few observations: no pass thread owns all SW_PF quads, the statistics leave the unrolled work of the missing ones out)
 __global__ __launch_bounds__(FBLOCK) void k_sweep_few(BartArrays aKern, SweepArgs xKern) { sweep_body<false, true>(aKern, xKern); }
 __global__ __launch_bounds__(FBLOCK) void k_sweep_stream(BartArrays aKern, SweepArgs xKern) { sweep_body<true, false>(aKern, xKern); }
-// (cgm(split.probs): the same launches with the weighted predictor choice compiled into the wave-register control code — WaveModelT<true>, dev_hip.hip)
+// (cgm(split.probs): the same launches with the weighted predictor choice compiled into the wave-register control code — WaveModelT<true>, dev_control.hpp)
 __global__ __launch_bounds__(FBLOCK) void k_sweep_sp(BartArrays aKern, SweepArgs xKern) { sweep_body<false, false, true>(aKern, xKern); }
 __global__ __launch_bounds__(FBLOCK) void k_sweep_few_sp(BartArrays aKern, SweepArgs xKern) { sweep_body<false, true, true>(aKern, xKern); }
 #if !S4B_LINEAR && S4B_WAVERED
@@ -2738,4 +2687,4 @@ __global__ __launch_bounds__(FBLOCK) void k_sbatch_w(const unsigned char* slots)
   if (threadIdx.x == 0) *((const SweepArgs*)(slots + (size_t)blockIdx.x * SW_SLOT_BYTES + SW_SLOT_XOFF))->status = -3;
 }
 #endif
-#endif   // S4B_SWEEP_TU
+}  // namespace s4b

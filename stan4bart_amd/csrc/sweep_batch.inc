@@ -5,10 +5,6 @@
 // the hardware values and the kernels of one sampler compile to the code they always had.
 #define SW_BX (BATCH ? 0u : blockIdx.x)
 #define SW_GX (BATCH ? 1u : gridDim.x)
-// one member's slot: its BartArrays, then its SweepArgs at the offset SW_KERNARGS reads them from
-constexpr size_t SW_SLOT_XOFF = (sizeof(BartArrays) + 7) / 8 * 8;
-constexpr size_t SW_SLOT_BYTES = (SW_SLOT_XOFF + sizeof(SweepArgs) + 255) / 256 * 256;
-static_assert(SW_SLOT_XOFF == (sizeof(BartArrays) + 7) / 8 * 8, "slot layout = kernarg layout");
 // (BATCH: the one kernel argument is the address of the slots; the member's arguments are read from its slot through the same constant
 // address space as the kernarg segment, so every argument load stays a scalar load)
 typedef const __attribute__((address_space(4))) unsigned char* sw_karg_ptr;
@@ -16,10 +12,3 @@ __device__ __forceinline__ sw_karg_ptr sw_batch_slot(sw_karg_ptr kp) {
   return (sw_karg_ptr)(*(const __attribute__((address_space(4))) unsigned long long*)kp + (unsigned long long)blockIdx.x * SW_SLOT_BYTES);
 }
 #define SW_SLOT_OF(kp) if constexpr (BATCH) kp = sw_batch_slot(kp)      // (no do-while: a loop scope would renumber the cleanup destinations of every kernel)
-#ifndef S4B_SWEEP_TU
-__global__ __launch_bounds__(FBLOCK) void k_sbatch(const unsigned char* slots);
-__global__ __launch_bounds__(FBLOCK) void k_sbatch_few(const unsigned char* slots);
-__global__ __launch_bounds__(FBLOCK) void k_sbatch_sp(const unsigned char* slots);
-__global__ __launch_bounds__(FBLOCK) void k_sbatch_few_sp(const unsigned char* slots);
-__global__ __launch_bounds__(FBLOCK) void k_sbatch_w(const unsigned char* slots);      // (a stub in the build variants without k_sweep_w: never launched there)
-#endif

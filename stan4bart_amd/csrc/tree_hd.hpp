@@ -11,7 +11,7 @@
 // propose()/decide() never touch per-observation data.  They are written against an abstract array
 // accessor (get/set), so the same source runs
 //   * on the device with every small array spread over the 64 lanes of one wavefront and read
-//     with v_readlane (WaveArr in dev_hip.hip) — wave-uniform scalar code with ~register latency —
+//     with v_readlane (WaveArr in dev_control.hpp) — wave-uniform scalar code with ~register latency —
 //     or on LDS/global pointers for trees with more than 64 node slots,
 //   * on the host on plain pointers (tree initialisation; CPU tests of the host logic).
 // The move definitions, draw order and probabilities are those written down in

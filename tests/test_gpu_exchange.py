@@ -1,4 +1,4 @@
-"""The persistent sweep's exchange at the edges of its fixed-point format (xc_publish, stan4bart_amd/csrc/dev_step.inc): every pass workgroup adds
+"""The persistent sweep's exchange at the edges of its fixed-point format (xc_publish, stan4bart_amd/csrc/dev_step_shared.hpp): every pass workgroup adds
 its partial (sum, count) of a bin into copy blockIdx % 8 as two 64-bit words, the sum at an absolute resolution of 2^-55, the count in a 21-bit
 field.  Two admissions of the host (dev_hip.hip, creation of the device arrays) keep samplers inside that format, and both are tested at their edges:
 
