@@ -367,6 +367,14 @@ int S4B_FN(profile_leapfrog)(s4b_sampler* s, int32_t n_evals, double out[8]);
  * fallback of the persistent path runs under the parity tests without a second process; value 0 switches it off.  Other hooks are rejected. */
 int S4B_FN(set_test_hook)(s4b_sampler* s, int32_t hook, int64_t value);
 
+/* TEST ENTRY (no reference counterpart): ONE draw of the probit latents from the state as it stands, and nothing else of a sweep — the exact
+ * draw of latent mode 0 (dbarts' sequential truncated normals from R's stream: k_latents2 + k_latents_finish on the device), then a wait and
+ * the check of the device error word.  With set_state before it (r_rng, offset, total_fits, latents) and get_state after it, a test chooses the
+ * 624 state words, mti, fits, offsets and previous latents the draw sees, which run() cannot offer: its tree sweep consumes a data-dependent
+ * number of stream positions first.  Refused for a continuous response, in latent mode 1 and on a stored sampler.  Domain of the device draw:
+ * an observation that needs more than 256 stream positions fails with "internal error" (DESIGN.md 5.4, 7). */
+int S4B_FN(test_draw_latents)(s4b_sampler* s);
+
 /* finalizer of the externalptr — src/init.cpp:1152-1165 */
 void S4B_FN(free)(s4b_sampler* s);
 

@@ -245,6 +245,7 @@ class BartFit {
   }
 
   // dbarts storeLatents (reference src/init.cpp:289,845)
+  void drawLatentsOnly() { sampleProbitLatents(); }      // orc_test_draw_latents: the latent draw alone, from the state as it stands
   void getLatents(double* out) const { for (size_t i = 0; i < n; ++i) out[i] = probitLatents[i] + offset[i]; }
 
   // canonical serialisation for parity tests: preorder (var, split), leaves as (-1, count)

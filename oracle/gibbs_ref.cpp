@@ -539,6 +539,15 @@ int orc_set_state(s4b_sampler* s, const void* buf, int64_t size) {
     return 0;
   } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
+// TEST ENTRY (include/stan4bart_amd.h, s4b_test_draw_latents): one draw of the probit latents from the state as it stands
+int orc_test_draw_latents(s4b_sampler* s) {
+  try {
+    if (!s || s->stored) throw std::invalid_argument("this call needs a live sampler");
+    if (!s->binary) throw std::invalid_argument("test_draw_latents: this sampler's response is continuous (no probit latents)");
+    s->bart->drawLatentsOnly();      // (sampleProbitLatents)
+    return 0;
+  } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
 void orc_free(s4b_sampler* s) { delete s; }
 
 // ---- small extras used only by tests: direct access to the RNG restatements and the model ----

@@ -303,7 +303,7 @@ class Sampler:
             "profile_sweep": [vp, i32, dp], "profile_leapfrog": [vp, i32, dp],
             "set_progress": [vp, PROGRESS, vp], "set_device_sharing": [vp, i32],
             "set_tree_path": [vp, i32], "get_tree_path": [vp, ip], "get_fused_stats": [vp, C.POINTER(i64)], "get_sweep_stats": [vp, C.POINTER(i64)], "get_sweep_busy": [vp, C.POINTER(i64)], "get_sweep_spec": [vp, C.POINTER(i64)], "set_test_hook": [vp, i32, i64], "set_hmc_mode": [vp, i32], "get_hmc_mode": [vp, ip],
-            "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip],
+            "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp],
         }
         for name, argtypes in sig.items():
             fn = getattr(self._lib, self._pfx + name, None)
@@ -537,6 +537,11 @@ class Sampler:
     def set_test_hook(self, hook: int, value: int):
         """TEST HOOK (include/stan4bart_amd.h): hook 1, value k — every k-th persistent launch reports a busy device (0 = off)."""
         self._check(self._f("set_test_hook")(self._h, int(hook), int(value)))
+
+    def test_draw_latents(self):
+        """TEST ENTRY (include/stan4bart_amd.h): one exact draw of the probit latents from the current state (``set_state`` before, ``get_state``
+        after), nothing else of a sweep."""
+        self._check(self._f("test_draw_latents")(self._h))
 
     def get_sweep_busy(self) -> int:
         """Persistent launches that found the device shared (roll call failed; their sweeps ran as k_step launches) since creation."""

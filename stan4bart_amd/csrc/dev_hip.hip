@@ -1039,7 +1039,9 @@ __global__ __launch_bounds__(LB2) void k_latents2(BartArrays a, double* xacc) {
   // returns (2 positions), E[p] / EL[p] = the value an exp_rand() starting at p returns and the positions it consumes (<= 18)
   auto refill = [&]() {   // uniform control flow: every thread executes the same sequence of barriers
     bool any = false;
-    while ((long long)624 * nblk - base < 1536 && (long long)624 * (nblk + 1) - base <= L_RING) {
+    // at least 1536 and fewer than 1536 + 624 positions ahead of base afterwards: well inside the ring, and far more than one batch can read
+    // (2 (L_NB - 1) + 63 of start, two ballots of 64, 256 of one observation: tests/test_latents_exact.py walks the reachable (base, nblk))
+    while ((long long)624 * nblk - base < 1536) {
       uint32_t* src = S.mt[(nblk - 1) % L_BLK]; uint32_t* dst = S.mt[nblk % L_BLK];
       if (wv == 0) {
         for (int i = lane; i < 624; i += 64) dst[i] = src[i];
@@ -1129,9 +1131,10 @@ __global__ __launch_bounds__(LB2) void k_latents2(BartArrays a, double* xacc) {
           next = p;
         }
         const long long sl = next - (p0 + lane) + lane - 2;      // slack of the next observation
-        // (a slack beyond the 8-bit table — one observation consuming more than ~250 positions — is treated like a candidate that ran
-        // out of generated positions: the chain stops before it; were it the first observation of a batch with the ring full, the
-        // batch makes no progress and the kernel raises S4B_ERR_INTERNAL below instead of continuing from a wrong position)
+        // (a slack beyond the 8-bit table is treated like a candidate that ran out of generated positions: the chain stops before it and
+        // the observation opens the next batch at slack 0.  There it may consume up to 256 positions — 127 rejected normals —, the kernel's
+        // domain; beyond that the batch resolves nothing and the kernel raises S4B_ERR_INTERNAL below instead of continuing from a wrong
+        // position: DESIGN.md 5.4, 7)
         S.T[i][lane] = (bad || sl > 254) ? (uint8_t)255 : (uint8_t)sl;
         S.X[i][lane] = x;
       }
@@ -1167,8 +1170,9 @@ __global__ __launch_bounds__(LB2) void k_latents2(BartArrays a, double* xacc) {
         if (lane < cnt) xacc[c0 + done + lane] = S.X[lane][mine];
         if (lane == 0) {
           shBase = base + 2 * cnt + o; shCnt = cnt;
-          // no progress although the ring is as full as it can get: one observation would need thousands of positions
-          shStop = (cnt == 0 && (long long)624 * (nblk + 1) - base > L_RING && (long long)624 * nblk - base >= 1536) ? 1 : 0;
+          // a batch that resolves nothing: refill() has left >= 1536 positions ahead, so its first observation, from slack 0, needs more than the
+          // 256 positions the table can express.  Every pass of the batch loop thus either resolves an observation or ends the kernel.
+          shStop = cnt == 0 ? 1 : 0;
         }
       }
       __syncthreads();
@@ -2327,6 +2331,7 @@ class DevHip {
       launches_ += 2;
     } else { hipLaunchKernelGGL(k_latents, dim3(1), dim3(BLOCK), 0, stream_, a_); ++launches_; }
   }
+  void test_draw_latents() { launch_latents(); sync(); }   // s4b_test_draw_latents: the latent draw alone (the caller checks the error word)
   void launch_step(int t) {
     if (a_.wts) hipLaunchKernelGGL((k_step<true>), dim3(a_.gridF), dim3(FBLOCK), ldsStep_, stream_, a_, t);
     else hipLaunchKernelGGL((k_step<false>), dim3(a_.gridF), dim3(FBLOCK), ldsStep_, stream_, a_, t);

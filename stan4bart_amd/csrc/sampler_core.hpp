@@ -55,6 +55,9 @@ struct DevInit {
 // does the device layer draw the probit latents in parallel (latent mode 1: set_latent_mode, latent_state, set_latent_state)?
 template <class D, class = void> struct has_latent_mode : std::false_type {};
 template <class D> struct has_latent_mode<D, std::void_t<decltype(&D::set_latent_mode)>> : std::true_type {};
+// does the device layer offer the latent draw on its own (s4b_test_draw_latents)?  A layer without it still builds; the entry is refused there.
+template <class D, class = void> struct has_test_draw_latents : std::false_type {};
+template <class D> struct has_test_draw_latents<D, std::void_t<decltype(&D::test_draw_latents)>> : std::true_type {};
 
 template <class Dev>
 class SamplerCore {
@@ -653,6 +656,14 @@ class SamplerCore {
     if constexpr (kLatentMode) { dev_.set_latent_mode(mode, latKey_); latMode_ = mode; }
     else throw std::invalid_argument("this device layer has no parallel latent draw: latent mode 1 needs the HIP device layer");
   }
+  // TEST ENTRY (s4b_test_draw_latents): one exact latent draw from the state as it stands (set_state), nothing else of a sweep
+  void test_draw_latents() {
+    live();
+    if (!binary_) throw std::invalid_argument("test_draw_latents: this sampler's response is continuous (no probit latents)");
+    if (latMode_ != 0) throw std::invalid_argument("test_draw_latents: the sampler is in latent mode 1 (parallel); the entry draws the exact latents of mode 0");
+    if constexpr (has_test_draw_latents<Dev>::value) { dev_.test_draw_latents(); check_device(); }
+    else throw std::invalid_argument("test_draw_latents: this device layer has no latent draw on its own");
+  }
   int64_t get_trace(int64_t cap, int32_t* out) { live(); return dev_.get_trace(cap, out); }
   void leaf_assignment(int t, int32_t* out) {
     live();
@@ -971,7 +982,7 @@ class SamplerCore {
     int32_t e = dev_.error_flags();
     if (e & S4B_ERR_NODE_CAPACITY) throw std::runtime_error("a tree outgrew node_capacity; re-create the sampler with a larger bart_control.node_capacity");
     if (e & S4B_ERR_I_LATENT) throw std::runtime_error("parallel latents: no proposal was accepted for an observation (a non-finite mean; device error word " + std::to_string(e) + ")");
-    if (e & S4B_ERR_INTERNAL) throw std::runtime_error("internal error: a hand-shake of the control kernel timed out (device error word " + std::to_string(e) + ")");
+    if (e & S4B_ERR_INTERNAL) throw std::runtime_error("internal error: a hand-shake of the control kernel timed out, or one probit latent needed more than 256 positions of R's stream (device error word " + std::to_string(e) + ")");
     if (e & S4B_ERR_TRACE_OVERFLOW) throw std::runtime_error("trace buffer overflow: call get_trace more often");
   }
 

@@ -236,6 +236,7 @@ class DevCpu {
       R_[i] = lat_[i] - F;
     }
   }
+  void test_draw_latents() { sample_latents(); }   // s4b_test_draw_latents: the latent draw alone
   void predict_stored(const uint16_t* xb, int64_t nT, const PackedNode* nodes, size_t, const int64_t* treeStart, int64_t S, int T, const double* scale,
                       int binary, double* out) {
     for (int64_t k = 0; k < S; ++k) for (int64_t i = 0; i < nT; ++i) {
