@@ -375,6 +375,16 @@ int S4B_FN(set_test_hook)(s4b_sampler* s, int32_t hook, int64_t value);
  * an observation that needs more than 256 stream positions fails with "internal error" (DESIGN.md 5.4, 7). */
 int S4B_FN(test_draw_latents)(s4b_sampler* s);
 
+/* TEST ENTRY (no reference counterpart): the Stan -> BART hand-off of ONE Gibbs iteration and nothing else — exactly what run() does between
+ * the Stan transition and the tree sweep (reference src/init.cpp:762-821), for coefficients the caller chooses: BART's offset from beta (K) and
+ * b (q) with the terms of the sampler's own offset type (the same dispatch run() goes through), sigma (a continuous response only; ignored for a
+ * binary one) and the rescaling of the response, with a new response scale when update_scale != 0; then the check of the device error word.  No
+ * transition, no sweep, no latent draw, no refresh of the Stan block's inputs: Stan's position, its adaptation state and both generators are left
+ * alone, so a get_state after the call differs from one before it in the BART block's scale, offset, total fits, leaf values and latents only,
+ * and a test can compare exactly those.  The coefficients need not be a draw of the model (they are not stored: get_parametric_mean keeps
+ * answering from the last transition).  Refused on a stored sampler, for non-finite coefficients and for a sigma that is not positive. */
+int S4B_FN(test_hand_off)(s4b_sampler* s, const double* beta, const double* b, double sigma, int32_t update_scale);
+
 /* finalizer of the externalptr — src/init.cpp:1152-1165 */
 void S4B_FN(free)(s4b_sampler* s);
 

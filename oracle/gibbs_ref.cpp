@@ -548,6 +548,33 @@ int orc_test_draw_latents(s4b_sampler* s) {
     return 0;
   } catch (const std::exception& e) { g_err = e.what(); return 1; }
 }
+// TEST ENTRY (include/stan4bart_amd.h, s4b_test_hand_off): the offset / sigma / rescaling step of orc_run for given coefficients, nothing else
+int orc_test_hand_off(s4b_sampler* sp, const double* beta, const double* b, double sigma, int32_t update_scale) {
+  try {
+    if (!sp || sp->stored) throw std::invalid_argument("this call needs a live sampler");
+    s4b_sampler& s = *sp;
+    const size_t n = s.n;
+    const StanModel& m = *s.model;
+    if ((m.dat.K > 0 && !beta) || (m.dat.q > 0 && !b)) throw std::invalid_argument("test_hand_off: NULL coefficients");
+    for (int k = 0; k < m.dat.K; ++k) if (!std::isfinite(beta[k])) throw std::invalid_argument("test_hand_off: non-finite coefficient");
+    for (int j = 0; j < m.dat.q; ++j) if (!std::isfinite(b[j])) throw std::invalid_argument("test_hand_off: non-finite coefficient");
+    if (!s.binary && (!(sigma > 0.0) || !std::isfinite(sigma))) throw std::invalid_argument("test_hand_off: sigma must be positive and finite");
+    std::vector<double> cons((size_t)(m.b_pos() + m.dat.q), 0.0);
+    for (int k = 0; k < m.dat.K; ++k) cons[(size_t)(m.beta_pos() + k)] = beta[k];
+    for (int j = 0; j < m.dat.q; ++j) cons[(size_t)(m.b_pos() + j)] = b[j];
+    const bool user = s.hasUserOffset;
+    const bool fixed = !user || s.offsetType == OFFSET_DEFAULT || s.offsetType == OFFSET_BART || s.offsetType == OFFSET_RANEF;
+    const bool random = !user || s.offsetType == OFFSET_DEFAULT || s.offsetType == OFFSET_BART || s.offsetType == OFFSET_FIXEF;
+    if (user && s.offsetType == OFFSET_PARAMETRIC) s.bartOffset = s.userOffset;
+    else {
+      m.parametric_mean(cons.data(), s.bartOffset.data(), fixed, random);
+      if (user && s.offsetType != OFFSET_BART) for (size_t j = 0; j < n; ++j) s.bartOffset[j] += s.userOffset[j];
+    }
+    if (!s.binary) s.bart->setSigma(sigma);
+    s.bart->setOffset(s.bartOffset.data(), update_scale != 0);
+    return 0;
+  } catch (const std::exception& e) { g_err = e.what(); return 1; }
+}
 void orc_free(s4b_sampler* s) { delete s; }
 
 // ---- small extras used only by tests: direct access to the RNG restatements and the model ----

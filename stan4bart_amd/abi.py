@@ -303,7 +303,7 @@ class Sampler:
             "profile_sweep": [vp, i32, dp], "profile_leapfrog": [vp, i32, dp],
             "set_progress": [vp, PROGRESS, vp], "set_device_sharing": [vp, i32],
             "set_tree_path": [vp, i32], "get_tree_path": [vp, ip], "get_fused_stats": [vp, C.POINTER(i64)], "get_sweep_stats": [vp, C.POINTER(i64)], "get_sweep_busy": [vp, C.POINTER(i64)], "get_sweep_spec": [vp, C.POINTER(i64)], "set_test_hook": [vp, i32, i64], "set_hmc_mode": [vp, i32], "get_hmc_mode": [vp, ip],
-            "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp],
+            "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
         }
         for name, argtypes in sig.items():
             fn = getattr(self._lib, self._pfx + name, None)
@@ -542,6 +542,12 @@ class Sampler:
         """TEST ENTRY (include/stan4bart_amd.h): one exact draw of the probit latents from the current state (``set_state`` before, ``get_state``
         after), nothing else of a sweep."""
         self._check(self._f("test_draw_latents")(self._h))
+
+    def test_hand_off(self, beta, b, sigma: float, update_scale: bool):
+        """TEST ENTRY (include/stan4bart_amd.h): the Stan -> BART hand-off of one iteration for the given coefficients (BART's offset by the sampler's
+        offset type, sigma, the rescaling with or without a new response scale) and nothing else; Stan's position and both generators stay."""
+        beta, b = _f64(np.atleast_1d(beta)), _f64(np.atleast_1d(b))
+        self._check(self._f("test_hand_off")(self._h, _dp(beta) if beta.size else None, _dp(b) if b.size else None, float(sigma), int(bool(update_scale))))
 
     def get_sweep_busy(self) -> int:
         """Persistent launches that found the device shared (roll call failed; their sweeps ran as k_step launches) since creation."""

@@ -304,14 +304,7 @@ class SamplerCore {
         const double* cons = row_.data() + 7;
         const double* beta = cons + model_->sp.beta_pos();
         const double* b = cons + model_->sp.b_pos();
-        if (!hasUserOffset_) dev_.offset_from_params(beta, b, 1, 1, 0);
-        else switch (offsetType_) {
-          case OFFSET_DEFAULT: dev_.offset_from_params(beta, b, 1, 1, 1); break;
-          case OFFSET_BART: dev_.offset_from_params(beta, b, 1, 1, 0); break;
-          case OFFSET_RANEF: dev_.offset_from_params(beta, b, 1, 0, 1); break;
-          case OFFSET_FIXEF: dev_.offset_from_params(beta, b, 0, 1, 1); break;
-          case OFFSET_PARAMETRIC: dev_.offset_from_params(beta, b, 0, 0, 1); break;
-        }
+        offset_by_type(beta, b);
         if (!binary_) { sigma_ = cons[model_->sp.aux_pos()]; dev_.set_sigma(sigma_); }
         if (out && out->stan) std::memcpy(out->stan + slot * (size_t)numPars, row_.data(), (size_t)numPars * sizeof(double));
         int update_scale_mod = 1 << (8 * iter / numIter);
@@ -344,6 +337,31 @@ class SamplerCore {
     }
     if (timing) std::fprintf(stderr, "S4B host ms/iter: nuts %.3f  offset+rescale issue %.3f  sweep + stan inputs (wait) %.3f  results %.3f\n",
                              1e3 * tph[0] / numIter, 1e3 * tph[1] / numIter, 1e3 * tph[2] / numIter, 1e3 * tph[3] / numIter);
+    check_device();
+  }
+
+  // BART's offset from the parametric draw: which of X beta, Z b and the user's offset it holds is the sampler's offset type
+  // (reference src/init.cpp:762-795).  The one dispatch of run() and of the hand-off test entry.
+  void offset_by_type(const double* beta, const double* b) {
+    if (!hasUserOffset_) { dev_.offset_from_params(beta, b, 1, 1, 0); return; }
+    switch (offsetType_) {
+      case OFFSET_DEFAULT: dev_.offset_from_params(beta, b, 1, 1, 1); break;
+      case OFFSET_BART: dev_.offset_from_params(beta, b, 1, 1, 0); break;
+      case OFFSET_RANEF: dev_.offset_from_params(beta, b, 1, 0, 1); break;
+      case OFFSET_FIXEF: dev_.offset_from_params(beta, b, 0, 1, 1); break;
+      case OFFSET_PARAMETRIC: dev_.offset_from_params(beta, b, 0, 0, 1); break;
+    }
+  }
+  // TEST ENTRY (s4b_test_hand_off): what run() does between the Stan transition and the sweep, for a given (beta, b, sigma), and nothing else
+  void test_hand_off(const double* beta, const double* b, double sigma, bool updateScale) {
+    live();
+    if ((K_ > 0 && !beta) || (q_ > 0 && !b)) throw std::invalid_argument("test_hand_off: NULL coefficients");
+    for (int k = 0; k < K_; ++k) if (!std::isfinite(beta[k])) throw std::invalid_argument("test_hand_off: non-finite coefficient");
+    for (int j = 0; j < q_; ++j) if (!std::isfinite(b[j])) throw std::invalid_argument("test_hand_off: non-finite coefficient");
+    if (!binary_ && (!(sigma > 0.0) || !std::isfinite(sigma))) throw std::invalid_argument("test_hand_off: sigma must be positive and finite");
+    offset_by_type(beta, b);
+    if (!binary_) { sigma_ = sigma; dev_.set_sigma(sigma_); }
+    dev_.rescale(updateScale);
     check_device();
   }
 

@@ -106,7 +106,8 @@ class DevCpu {
     return m;
   }
 
-  // ---- offsets and response rescaling (dbarts setOffset / setSigma)
+  // ---- offsets and response rescaling (dbarts setOffset / setSigma).  s4b_test_hand_off (SamplerCore::test_hand_off) is offset_from_params + set_sigma + rescale
+  //      and nothing else, as in run(); there is no one-launch form to hold calls for here
   void offset_from_host(const double* off) { std::memcpy(offNew_.data(), off, n_ * 8); }
   void offset_from_params(const double* beta, const double* b, int fixed, int random, int addUser) {
     for (size_t i = 0; i < n_; ++i) {

@@ -109,6 +109,27 @@ def tree_starts(trees):
     return starts, end
 
 
+def walk_leaves(trees, x):
+    """The walk alone: for every tree of a flattened tree list, in order, the ENTRY index of the leaf that each raw row of `x` reaches ("go left iff
+    x <= cut value").  Yields (position of the tree in the list, its first entry, entry index per row).  walk_fits sums the leaf values found this
+    way; tests/handoff_cases.py (audit_state) compares the leaves themselves with the device's leaf assignment."""
+    x = np.asarray(x, dtype=np.float64)
+    var, value = trees["var"], trees["value"]
+    starts, end = tree_starts(trees)
+    m = x.shape[0]
+    rows = np.arange(m)
+    for a, st in enumerate(starts):
+        pos = np.full(m, st, dtype=np.int64)
+        act = rows if var[st] >= 0 else rows[:0]
+        while len(act):
+            p = pos[act]
+            left = x[act, var[p]] <= value[p]
+            p = np.where(left, p + 1, end[p + 1])
+            pos[act] = p
+            act = act[var[p] >= 0]
+        yield a, int(st), pos
+
+
 def walk_fits(trees, x, ranges, binary=False):
     """Fits [rows x draws] of the raw rows `x` under the flattened `trees` (get_kept_trees(): every kept draw; get_trees(): one draw), `ranges` the
     (min, max) of the response scale of every draw ([draws x 2], or one pair for all).  Returns (fits as float64, the bound of the module docstring per
@@ -122,18 +143,9 @@ def walk_fits(trees, x, ranges, binary=False):
     assert len(starts) == S * T and np.array_equal(draw, np.repeat(np.arange(S), T)) and np.array_equal(trees["tree"][starts], np.tile(np.arange(T), S))
     ranges = np.broadcast_to(np.asarray(ranges, dtype=np.float64).reshape(-1, 2), (S, 2))
     m = x.shape[0]
-    rows = np.arange(m)
     f = np.zeros((m, S), dtype=np.longdouble)
     fabs = np.zeros((m, S), dtype=np.longdouble)
-    for a, st in enumerate(starts):
-        pos = np.full(m, st, dtype=np.int64)
-        act = rows if var[st] >= 0 else rows[:0]
-        while len(act):
-            p = pos[act]
-            left = x[act, var[p]] <= value[p]
-            p = np.where(left, p + 1, end[p + 1])
-            pos[act] = p
-            act = act[var[p] >= 0]
+    for a, st, pos in walk_leaves(trees, x):
         mu = value[pos].astype(np.longdouble)
         f[:, draw[a]] += mu
         fabs[:, draw[a]] += np.abs(mu)
