@@ -1841,7 +1841,7 @@ class DevHip {
         // (observation weights: k_sweep_w keeps the workgroup's 4 096 weights in 32 KiB of LDS beside the tables; not together with split.probs,
         // not on the streaming variant)
         weighted_ = d.weights != nullptr;
-        constexpr bool weightedSweepBuilt = !S4B_LINEAR && S4B_WAVERED;      // (the build variants with another reduction of the statistics have no k_sweep_w: weighted samplers take the per-tree kernels there)
+        constexpr bool weightedSweepBuilt = !S4B_LINEAR;      // (the linear variant has no k_sweep_w: weighted samplers take the per-tree kernels there)
         size_t staticLds = 40 * 1024;
         if (weighted_ && weightedSweepBuilt) { hipFuncAttributes fa; HIP_OK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_sweep_w))); staticLds = fa.sharedSizeBytes + 512; }      // (its static part: tables + 32 KiB of weights)
         double wMin = 0.0, wMax = 0.0;

@@ -125,22 +125,9 @@ void sweep_decide_fetch(unsigned long long* out) {   // (reads and clears)
 #define SW_A(i)
 #define SW_AP(i)
 #endif
+constexpr int S4B_PRIO_DEC = 1, S4B_PRIO_IMG = 1, S4B_PRIO_XCH = 3, S4B_PRIO_SPEC = 2;   // wave priorities: decider, image waves, exchange wave, a pass wave in its speculative statistics
+constexpr int S4B_POLL_DELAY = 40, S4B_POLL_SLEEP = 2;     // the exchange wave's poll: s_sleep before the first look at the exchange words / between two looks
 constexpr long long SW_ROLL_TICKS = 20000;   // 200 us of the 100 MHz wall clock: a launch on a free device has all its workgroups running within a few microseconds
-#ifndef S4B_LFAHEAD
-#define S4B_LFAHEAD 0      // 1: the leaf ids of a step requested during the step before, in front of the wait for wave 3's leaf values (`make lfahead`).  Measured SLOWER, round 6:
-                           // 1 756 - 1 762 against 1 698 - 1 707 us per sweep, A/B/A/B/A/B — packing them is their first use, and the wait for the memory counter in front of it
-                           // stalls the wave in the steps in which the leaf values are already there
-#endif
-#ifndef S4B_PREBITS
-#define S4B_PREBITS 0      // 1: the bin bits and bin counts of a step's statistics gathered behind the routing, off the chain of the step (needs S4B_WAVERED; `make prebits`).  Measured
-                           // SLOWER, round 6: 1 761 - 1 776 against 1 716 - 1 725 us per sweep, same box A/B/A/B — the window behind the routing is not idle enough for 0.7 us more
-#endif
-#ifndef S4B_X1
-#define S4B_X1 0      // (1: the arrival behind the ahead pass waits for the wave's LDS counter only — measured: the chain then differs from the oracle's in one run of four; 0: a release fence)
-#endif
-#ifndef S4B_X2
-#define S4B_X2 1
-#endif
 
 struct SweepModel { double pg[64], lpg[64], l1pg[64], li0[64], li1[64]; int nc0[64], nc1[64]; double sigma; };
 struct SweepShared {
@@ -432,7 +419,7 @@ __device__ __forceinline__ void sweep_route(const BartArrays& a, const NodeS* co
   }
 }
 // statistics of one bin pass: per-thread sums of the partial residual rs over the NB bins [base, base + NB) — A bin (current leaf)
-// and B bin (leaf the proposal creates) of every observation —, block reduction over the pass waves in a fixed order, and the
+// and B bin (leaf the proposal creates) of every observation —, reduction over the pass waves in a fixed order, and the
 // workgroup's contribution to the exchange words.  NB is the EXACT number of bins (the cost of the accumulation is observations x
 // bins x 4 instructions: per observation a two-bit one-hot word, per bin a bit extract, the 0.0 / 1.0 factor, one fused
 // multiply-add — exact: the product is rs or 0 — and one integer add for the count).
@@ -455,10 +442,10 @@ template <int NB, bool SKIP, bool LIN, bool WT = false, bool BATCH = false>
 __device__ __forceinline__ bool sweep_stats(const BartArrays& a, const SweepLds& L, PassBar& bar, const double (&r)[SW_PF][4], const lfq_t (&lf)[SW_PF], const NodeS* __restrict__ Ssel,
                                             const unsigned (&bb)[SW_PF], int64_t q0, int64_t stride, int64_t nQuads, int base, unsigned long long* xcur, double* part_,
                                             bool alsoPart, int pw, int lane, long long tRef = 0,
-                                            const lfq_t (*foldLf)[SW_PF] = nullptr, const NodeA* __restrict__ foldA = nullptr, double* heldS = nullptr, int* heldC = nullptr, int jMax = SW_PF,
+                                            const lfq_t (*foldLf)[SW_PF] = nullptr, const NodeA* __restrict__ foldA = nullptr, int jMax = SW_PF,
                                             const lfq_t (*keyLf)[SW_PF] = nullptr, unsigned* ctab = nullptr, double* preS = nullptr, const double* __restrict__ foldD = nullptr,
                                             const double* __restrict__ wq = nullptr, int nbAll = 0, double wScale = 1.0) {
-  static_assert(!WT || (S4B_WAVERED && !LIN), "the weighted statistics exist for the per-wave reduction of the default build only");
+  static_assert(!WT || !LIN, "the weighted statistics exist in the default build only, not in the ahead pass of the linear one");
 #ifdef S4B_SWEEP_TIMING
 #define SWS_T(i, cond) do { if ((int)SW_BX == SW_TIMED_WG && lane == 0 && tRef != 0 && (cond)) atomicAdd(&bar.tacc[i], (unsigned long long)(wall_clock64() - tRef)); } while (0)
 #else
@@ -526,17 +513,6 @@ __device__ __forceinline__ bool sweep_stats(const BartArrays& a, const SweepLds&
     }
   }
   SWS_T(30, pw == 1);
-  // block reduction through LDS, transposed: every pass thread leaves its NB partials in the rows of the bins (one LDS write per
-  // value, no cross-lane exchange); after the barrier ONE wave folds them: lane 8 k + part adds entries part, part + 8, ... of bin k
-  // in order, three xor exchanges combine the eight parts — a fixed order, ~40 instructions instead of ~250 for the register
-  // butterfly of sums and counts in every wave
-  {
-    const int col = pw * 64 + lane;
-    if (!LIN && !S4B_WAVERED) {
-#pragma unroll
-      for (int k = 0; k < NB; ++k) { L.redS[k * SW_RED_ROW + col] = accS[k]; L.redN[k * SW_RED_ROW + col] = accN[k]; }
-    }
-  }
   SWS_T(31, pw == 1);
   if constexpr (LIN) {
     // the ahead pass: every pass wave sums ITS 64 lanes in registers — halving exchanges: NB - 1 + log2(64 / NB) of them, a fixed order — and leaves one pre-sum per
@@ -550,155 +526,23 @@ __device__ __forceinline__ bool sweep_stats(const BartArrays& a, const SweepLds&
     if ((lane & (64 / NP2 - 1)) == 0 && b < NB) preS[pw * 8 + b] = v[0];
     return false;
   }
-#if S4B_WAVERED
-  {
-    // Round 6: no block reduction.  Every pass wave sums its 64 lanes in registers (halving exchanges, a fixed order) and leaves one partial per bin; the LAST of the
-    // four waves to arrive adds the four partials in the order of the waves and publishes — nobody waits at a barrier, no 256-entry fold by one wave behind it
-    // (the statistics sit on the chain of a step: 2.6 us with the barrier, of which 0.7 us barrier and 0.45 us fold).  Returns whether this wave was the last.
-    constexpr int NP2 = NB <= 4 ? 4 : 8;
-    double v[NP2]; int cn[NP2];
-#pragma unroll
-    for (int k = 0; k < NP2; ++k) { v[k] = k < NB ? accS[k] : 0.0; cn[k] = k < NB ? accN[k] : 0; }
-    wave_sum_bins<NP2>(v, lane); wave_sum_bins<NP2>(cn, lane);
-    const int b = wave_bin_of_lane<NP2>(lane);
-    if ((lane & (64 / NP2 - 1)) == 0 && b < NB) { L.redS[pw * 8 + b] = v[0]; L.redN[pw * 8 + b] = cn[0]; }
-    if constexpr (WT) {
-      double vw[NP2];
-#pragma unroll
-      for (int k = 0; k < NP2; ++k) vw[k] = k < NB ? accW[WT ? k : 0] : 0.0;
-      wave_sum_bins<NP2>(vw, lane);
-      if ((lane & (64 / NP2 - 1)) == 0 && b < NB) L.redS[32 + pw * 8 + b] = vw[0];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    int old = 0;
-    if (lane == 0) old = __hip_atomic_fetch_add(bar.arr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    old = __builtin_amdgcn_readfirstlane(old);
-    if (old != SW_PW - 1) return false;
-    if (lane == 0) __hip_atomic_store(bar.arr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    const int k = lane < NB ? lane : 0;
-    const double sm = ((L.redS[k] + L.redS[8 + k]) + L.redS[16 + k]) + L.redS[24 + k];
-    const int c = ((L.redN[k] + L.redN[8 + k]) + L.redN[16 + k]) + L.redN[24 + k];
-    double wsum = 0.0;
-    if constexpr (WT) wsum = ((L.redS[32 + k] + L.redS[40 + k]) + L.redS[48 + k]) + L.redS[56 + k];
-    if (lane < NB) {
-      if (alsoPart) {
-        const size_t kind = (size_t)a.binCap * a.gridF;
-        part_[(size_t)(base + k) * a.gridF + SW_BX] = sm;
-        part_[kind + (size_t)(base + k) * a.gridF + SW_BX] = (double)c;
-        if (WT) part_[2 * kind + (size_t)(base + k) * a.gridF + SW_BX] = wsum;
-      }
-      // (WT: the instantiation may carry more bins than the step has left — NB = 3 for two —: without weights the surplus lands in slots nobody reads; here the slots
-      // behind the last bin ARE the sums of the weights)
-      if (WT && base + k >= nbAll) { }
-      else if (bar.solo) { bar.totS[base + k] = sm; bar.totC[base + k] = (double)c; if (WT) bar.totS[nbAll + base + k] = wsum; }
-      else if (WT) { xc_publish(xcur, base + k, sm * wScale, c, a.errFlag); xc_publish(xcur, nbAll + base + k, wsum * wScale, 0, a.errFlag); }
-      else xc_publish(xcur, base + k, sm, c, a.errFlag);
-    }
-    return true;
-  }
-#else
-  pass_barrier(bar);
-  SWS_T(32, pw == 1);
-  SWS_T(33, pw == 0);
-  if (pw == 0) {
-    // (the lane id taken afresh: values derived from the one the kernel started with stay live across the whole step otherwise — in scratch
-    // memory, for want of registers —, and their reloads sit on the way from the barrier to the publishing atomics)
-    const int ln = sweep_fresh_lane();
-    const int k = ln >> 3, part = ln & 7;
-    const int kk = k < NB ? k : 0;
-    double s0 = 0.0, s1 = 0.0; int c = 0;
-#pragma unroll
-    for (int i = 0; i < SW_PT / 8; i += 2) {
-      s0 += L.redS[kk * SW_RED_ROW + i * 8 + part]; s1 += L.redS[kk * SW_RED_ROW + (i + 1) * 8 + part];
-      if (!LIN) c += L.redN[kk * SW_RED_ROW + i * 8 + part] + L.redN[kk * SW_RED_ROW + (i + 1) * 8 + part];
-    }
-    double sm = s0 + s1;
-    sm += wave_xor<1>(sm); sm += wave_xor<2>(sm); sm += wave_xor<4>(sm);
-    if (!LIN) { c += wave_xor<1>(c); c += wave_xor<2>(c); c += wave_xor<4>(c); }
-    if (LIN) { if (part == 0 && k < NB) preS[k] = sm; }     // (the workgroup's pre-sums: the exchange wave finishes and publishes them one step later)
-    else if (heldS) { *heldS = sm; *heldC = c; }     // (a one-workgroup launch that speculates: the reduction IS the total the decider is still reading — lane 8 k keeps bin k's until the verdict)
-    else if (part == 0 && k < NB) {
-      if (alsoPart) {
-        const size_t kind = (size_t)a.binCap * a.gridF;
-        part_[(size_t)(base + k) * a.gridF + SW_BX] = sm;
-        part_[kind + (size_t)(base + k) * a.gridF + SW_BX] = (double)c;
-      }
-      if (bar.solo) { bar.totS[base + k] = sm; bar.totC[base + k] = (double)c; }
-      else xc_publish(xcur, base + k, sm, c, a.errFlag);
-    }
-  }
-  return pw == 0;
-#endif
-}
-// Round 6: what the statistics of a step need of the TREE and the PROPOSAL, not of the residual — which bins an observation is counted in, and the bin counts — is
-// gathered in the window in which the pass waves only wait (behind the routing under image 0, before wave 3's leaf values): one byte of bin bits per observation
-// (bitsQ) and the wave's bin counts in LDS (cntSlot[pw][8]).  The pass on the chain of the step (sweep_stats_pre) then reads one 8-byte leaf value and one 16-byte
-// fold record per observation and does three instructions per observation and bin.
-template <bool SKIP>
-__device__ __forceinline__ void sweep_bits(const BartArrays& a, const lfq_t (&lf)[SW_PF], const NodeS* __restrict__ Ssel, const unsigned (&bb)[SW_PF], int64_t q0, int64_t stride, int64_t nQuads,
-                                           int pw, int lane, int jMax, unsigned (&bitsQ)[SW_PF], int* cntSlot) {
-  int accN[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) accN[k] = 0;
-#pragma unroll
-  for (int j = 0; j < SW_PF; ++j) {
-    bitsQ[j] = 0u;
-    if (SKIP && j >= jMax) continue;
-    const int64_t qd = q0 + (int64_t)j * stride;
-    const int valid = qd < nQuads ? ((a.n - (qd << 2)) >= 4 ? 4 : (int)(a.n - (qd << 2))) : 0;
-    const unsigned l4[4] = LFQ4(lf[j]);
-    unsigned ba[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ba[e] = (unsigned)(int)Ssel[l4[e]].binA & 0xffu;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const unsigned okM = 0u - (unsigned)(e < valid);
-      const unsigned sa = ba[e], sb = (bb[j] >> (8 * e)) & 0xffu;
-      const unsigned bits = ((sa < 8u ? 1u << sa : 0u) | (sb < 8u ? 1u << sb : 0u)) & okM;
-      bitsQ[j] |= bits << (8 * e);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) accN[k] += (int)((bits >> k) & 1u);
-    }
-  }
-  wave_sum_bins<8>(accN, lane);
-  const int b = wave_bin_of_lane<8>(lane);
-  if ((lane & 7) == 0) cntSlot[pw * 8 + b] = accN[0];
-}
-template <int NB, bool SKIP>
-__device__ __forceinline__ bool sweep_stats_pre(const BartArrays& a, const SweepLds& L, PassBar& bar, const double (&r)[SW_PF][4], const lfq_t (&lf)[SW_PF], const NodeS* __restrict__ Ssel,
-                                                const unsigned (&bitsQ)[SW_PF], unsigned long long* xcur, int pw, int lane, const lfq_t (&foldLf)[SW_PF], const NodeA* __restrict__ foldA,
-                                                int jMax, const int* cntSlot) {
-  double accS[NB];
-#pragma unroll
-  for (int k = 0; k < NB; ++k) accS[k] = 0.0;
-#pragma unroll
-  for (int j = 0; j < SW_PF; ++j) {
-    if (SKIP && j >= jMax) continue;
-    const unsigned l4[4] = LFQ4(lf[j]), pl[4] = LFQ4(foldLf[j]);
-    double mu[4]; NodeA na[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { mu[e] = Ssel[l4[e]].mu; na[e] = foldA[pl[e]]; }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      double rv = r[j][e];
-      rv += na[e].muOld; rv -= na[e].muNew;      // (the previous tree folded in on the fly, as the fold after the verdict does it: the same bits)
-      const double rs = rv + mu[e];              // (an observation slot beyond n has no bits: its factor is 0.0 and its sum finite — residual 0, table entries of node 0)
-      const unsigned bits = (bitsQ[j] >> (8 * e)) & 0xffu;
-#pragma unroll
-      for (int k = 0; k < NB; ++k) {
-        const unsigned mk = (bits >> k) & 1u;
-        accS[k] = fma(__hiloint2double((int)(mk * 0x3ff00000u), 0), rs, accS[k]);
-      }
-    }
-  }
+  // Round 6: no block reduction.  Every pass wave sums its 64 lanes in registers (halving exchanges, a fixed order) and leaves one partial per bin; the LAST of the
+  // four waves to arrive adds the four partials in the order of the waves and publishes — nobody waits at a barrier, no 256-entry fold by one wave behind it
+  // (the statistics sit on the chain of a step: 2.6 us with the barrier, of which 0.7 us barrier and 0.45 us fold).  Returns whether this wave was the last.
   constexpr int NP2 = NB <= 4 ? 4 : 8;
-  double v[NP2];
+  double v[NP2]; int cn[NP2];
 #pragma unroll
-  for (int k = 0; k < NP2; ++k) v[k] = k < NB ? accS[k] : 0.0;
-  wave_sum_bins<NP2>(v, lane);
+  for (int k = 0; k < NP2; ++k) { v[k] = k < NB ? accS[k] : 0.0; cn[k] = k < NB ? accN[k] : 0; }
+  wave_sum_bins<NP2>(v, lane); wave_sum_bins<NP2>(cn, lane);
   const int b = wave_bin_of_lane<NP2>(lane);
-  if ((lane & (64 / NP2 - 1)) == 0 && b < NB) L.redS[pw * 8 + b] = v[0];
+  if ((lane & (64 / NP2 - 1)) == 0 && b < NB) { L.redS[pw * 8 + b] = v[0]; L.redN[pw * 8 + b] = cn[0]; }
+  if constexpr (WT) {
+    double vw[NP2];
+#pragma unroll
+    for (int k = 0; k < NP2; ++k) vw[k] = k < NB ? accW[WT ? k : 0] : 0.0;
+    wave_sum_bins<NP2>(vw, lane);
+    if ((lane & (64 / NP2 - 1)) == 0 && b < NB) L.redS[32 + pw * 8 + b] = vw[0];
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   int old = 0;
   if (lane == 0) old = __hip_atomic_fetch_add(bar.arr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -708,24 +552,30 @@ __device__ __forceinline__ bool sweep_stats_pre(const BartArrays& a, const Sweep
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   const int k = lane < NB ? lane : 0;
   const double sm = ((L.redS[k] + L.redS[8 + k]) + L.redS[16 + k]) + L.redS[24 + k];
-  const int c = ((cntSlot[k] + cntSlot[8 + k]) + cntSlot[16 + k]) + cntSlot[24 + k];
-  if (lane < NB) xc_publish(xcur, k, sm, c, a.errFlag);
+  const int c = ((L.redN[k] + L.redN[8 + k]) + L.redN[16 + k]) + L.redN[24 + k];
+  double wsum = 0.0;
+  if constexpr (WT) wsum = ((L.redS[32 + k] + L.redS[40 + k]) + L.redS[48 + k]) + L.redS[56 + k];
+  if (lane < NB) {
+    if (alsoPart) {
+      const size_t kind = (size_t)a.binCap * a.gridF;
+      part_[(size_t)(base + k) * a.gridF + SW_BX] = sm;
+      part_[kind + (size_t)(base + k) * a.gridF + SW_BX] = (double)c;
+      if (WT) part_[2 * kind + (size_t)(base + k) * a.gridF + SW_BX] = wsum;
+    }
+    // (WT: the instantiation may carry more bins than the step has left — NB = 3 for two —: without weights the surplus lands in slots nobody reads; here the slots
+    // behind the last bin ARE the sums of the weights)
+    if (WT && base + k >= nbAll) { }
+    else if (bar.solo) { bar.totS[base + k] = sm; bar.totC[base + k] = (double)c; if (WT) bar.totS[nbAll + base + k] = wsum; }
+    else if (WT) { xc_publish(xcur, base + k, sm * wScale, c, a.errFlag); xc_publish(xcur, nbAll + base + k, wsum * wScale, 0, a.errFlag); }
+    else xc_publish(xcur, base + k, sm, c, a.errFlag);
+  }
   return true;
-}
-template <bool SKIP>
-__device__ __forceinline__ bool sweep_stats_pre_n(int n, const BartArrays& a, const SweepLds& L, PassBar& bar, const double (&r)[SW_PF][4], const lfq_t (&lf)[SW_PF], const NodeS* __restrict__ Ssel,
-                                                  const unsigned (&bitsQ)[SW_PF], unsigned long long* xcur, int pw, int lane, const lfq_t (&foldLf)[SW_PF], const NodeA* __restrict__ foldA,
-                                                  int jMax, const int* cntSlot) {
-  if (n <= 3) return sweep_stats_pre<3, SKIP>(a, L, bar, r, lf, Ssel, bitsQ, xcur, pw, lane, foldLf, foldA, jMax, cntSlot);
-  else if (n <= 4) return sweep_stats_pre<4, SKIP>(a, L, bar, r, lf, Ssel, bitsQ, xcur, pw, lane, foldLf, foldA, jMax, cntSlot);
-  else if (n <= 5) return sweep_stats_pre<5, SKIP>(a, L, bar, r, lf, Ssel, bitsQ, xcur, pw, lane, foldLf, foldA, jMax, cntSlot);
-  return sweep_stats_pre<8, SKIP>(a, L, bar, r, lf, Ssel, bitsQ, xcur, pw, lane, foldLf, foldA, jMax, cntSlot);
 }
 template <int NB, bool SKIP, bool LIN = false, bool WT = false, bool BATCH = false>
 __device__ __forceinline__ bool sweep_stats_n(int n, const BartArrays& a, const SweepLds& L, PassBar& bar, const double (&r)[SW_PF][4], const lfq_t (&lf)[SW_PF], const NodeS* __restrict__ Ssel,
                                               const unsigned (&bb)[SW_PF], int64_t q0, int64_t stride, int64_t nQuads, int base, unsigned long long* xcur, double* part,
                                               bool alsoPart, int pw, int lane, long long tRef = 0,
-                                              const lfq_t (*foldLf)[SW_PF] = nullptr, const NodeA* __restrict__ foldA = nullptr, double* heldS = nullptr, int* heldC = nullptr, int jMax = SW_PF,
+                                              const lfq_t (*foldLf)[SW_PF] = nullptr, const NodeA* __restrict__ foldA = nullptr, int jMax = SW_PF,
                                               const lfq_t (*keyLf)[SW_PF] = nullptr, unsigned* ctab = nullptr, double* preS = nullptr, const double* __restrict__ foldD = nullptr,
                                               const double* __restrict__ wq = nullptr, int nbAll = 0, double wScale = 1.0) {
   // (one instantiation per bin count would be many copies of the unrolled accumulation: with the control code of the other waves the hot
@@ -733,11 +583,13 @@ __device__ __forceinline__ bool sweep_stats_n(int n, const BartArrays& a, const 
   // usual proposals — a tree of 2-3 leaves + a birth, 4-6 leaves + a change — at a third more work than the exact count at most
   // (a 6-bin instantiation, round 5, stationary chain with 5.0 bins per step on average: 18 spilled registers instead of 14, sweep 2.21 instead of 2.165 ms);
   // more than 8 bins take several passes)
-  if (n <= 3) return sweep_stats<3, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
-  else if (n <= 4) return sweep_stats<4, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
-  else if (n <= 5) return sweep_stats<5, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
-  else if (n <= 8) return sweep_stats<8, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
-  else return sweep_stats<8, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, heldS, heldC, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  if (n <= 3) return sweep_stats<3, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  else if (n <= 4) return sweep_stats<4, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  else if (n <= 5) return sweep_stats<5, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  // (the last two branches are the same call and stay two: written as one, register allocation and scheduling of k_sweep* come out differently — 270 000 lines of its assembly —,
+  // which takes a measured A/B of its own, like the unreachable solo branch of the pass waves: DESIGN.md 5.0)
+  else if (n <= 8) return sweep_stats<8, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
+  else return sweep_stats<8, SKIP, LIN, WT, BATCH>(a, L, bar, r, lf, Ssel, bb, q0, stride, nQuads, base, xcur, part, alsoPart, pw, lane, tRef, foldLf, foldA, jMax, keyLf, ctab, preS, foldD, wq, nbAll, wScale);
 }
 
 
@@ -1114,13 +966,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
   // Priorities.  The control roles are dependent chains of wave-uniform code that share their SIMDs with the pass waves' bulk arithmetic.  Until round 5
   // they went first (3 against 0).  Since the statistics are published before the verdict the chain of a step is totals -> wave 3's leaf values ->
   // speculative statistics -> exchange: the exchange wave stays on top, the pass waves run their speculative statistics above the decider and the
-  // image waves, which have microseconds of slack per step (measured: 3 / 3 / 3 / 0 -> 423 it/s, 1 / 1 / 3 / 2 and 2 / 0 / 3 / 3 -> 438 - 445, 0 / 0 / 3 / 3 -> 435)
-#ifndef S4B_PRIO_DEC
-#define S4B_PRIO_DEC 1
-#define S4B_PRIO_IMG 1
-#define S4B_PRIO_XCH 3
-#define S4B_PRIO_SPEC 2
-#endif
+  // image waves, which have microseconds of slack per step (S4B_PRIO_*, measured: 3 / 3 / 3 / 0 -> 423 it/s, 1 / 1 / 3 / 2 and 2 / 0 / 3 / 3 -> 438 - 445, 0 / 0 / 3 / 3 -> 435)
   if (!STREAM) { if (wv == 0) __builtin_amdgcn_s_setprio(S4B_PRIO_DEC); else if (wv == 3) __builtin_amdgcn_s_setprio(S4B_PRIO_XCH); else if (wv < 3) __builtin_amdgcn_s_setprio(S4B_PRIO_IMG); }
   if (wv == 0) {
     // ====================================================================================== wave 0: the decider
@@ -1257,9 +1103,6 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
         // waves wait for goes out at once.  This wave still draws the leaves itself afterwards (its own state; checked against wave 3's).
         auto early = [&](int acc) -> bool {
           if (acc) return false;
-#ifdef S4B_NO_EARLY
-          return false;
-#endif
           int guard = 0, sp;
           while (((sp = __hip_atomic_load(&F.specReady, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) >> 1) < t) {
             __builtin_amdgcn_s_sleep(SW_SLEEP);
@@ -1624,12 +1467,6 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
         bool fine = true;
         // (the first poll waits ~1.1 us: this workgroup has just published, the last of the others is 1 - 2.5 us behind the first, and every
         // poll of the 256 workgroups is eight more requests to the cache lines the arriving atomics need — round 5: 467 -> 488 iterations/s)
-#ifndef S4B_POLL_DELAY
-#define S4B_POLL_DELAY 40
-#endif
-#ifndef S4B_POLL_SLEEP
-#define S4B_POLL_SLEEP 2
-#endif
         if (nw > 0 && !STREAM) __builtin_amdgcn_s_sleep(S4B_POLL_DELAY);
         for (int half = 0; half * 64 < nw; ++half) {
           const int wi = half * 64 + lane;
@@ -1726,7 +1563,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
 #ifdef S4B_SWEEP_WGD
             const long long tW0 = wall_clock64();
 #endif
-            if (prevOk && S4B_LINEAR != 2) spin_counter(&F.preDoneA, t, &F.abort); else spin_counter(&F.preDoneB, t, &F.abort);
+            if (prevOk) spin_counter(&F.preDoneA, t, &F.abort); else spin_counter(&F.preDoneB, t, &F.abort);
 #ifdef S4B_SWEEP_WGD
             if (lane == 0 && t > 1 && t + 1 < T && (int)SW_BX < 256) sw_dur_add((int)SW_BX * 64 + 7, (unsigned long long)(wall_clock64() - tW0));
 #endif
@@ -1952,7 +1789,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
         const double* foldD = L.dtab + (t & 1) * SW_NC;      // (differences old - new value of tree t-1: wave 3's, before specReady)
         if (phase == 0) {
           // ---- image 0 of tree t+1's proposal as wave 1 drew it AHEAD (during the step before this one)
-          if (S4B_LINEAR != 2 && !solo && spec && haveNext) {
+          if (!solo && spec && haveNext) {
             SW_D(0);
             if (!spin_counter(&F.pre0Ready, t + 1, &F.abort)) { quit = true; break; }
             SW_D(1);
@@ -1961,7 +1798,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
           }
         } else {
           // ---- the verdict is out: old leaf values, which observations move and where to
-          bool bothHalves = false, confirmedNow = false;
+          bool bothHalves = false;
           unsigned toP[SW_PF];      // node the observation ends up in (one byte per observation)
 #pragma unroll
           for (int j = 0; j < SW_PF; ++j) toP[j] = 0u;
@@ -1987,23 +1824,18 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
                 }
                 if (pw == 1) { SW_G(93); SW_W(11); }
                 SW_D(5);
-#if S4B_LINEAR == 2
-                confirmedNow = true;      // (IN-WINDOW mode: the pass for tree t+1 follows the fold of every step — see S4B_LINEAR)
-#else
                 break;
-#endif
               }
               // not borne out: what the ahead pass of this step counted is void — its tables are cleared before anybody counts into them again —, and
               // the reduction slots are free again once every pass wave is here
-              if (ranAhead && !confirmedNow) {
+              if (ranAhead) {
                 pass_barrier(bar);      // (the ahead pass has no barrier of its own: every pass wave must be through with its counting before the tables are cleared)
                 unsigned* const ct = L.ctab + (size_t)((t + 1) & 1) * SW_CT_WORDS;
                 for (int i = pw * 64 + lnP; i < SW_CT_WORDS; i += SW_PT) ct[i] = 0u;
               }
-              if ((hasObs || ranAhead) && !confirmedNow) pass_barrier(bar);
+              if (hasObs || ranAhead) pass_barrier(bar);
             }
-            if (confirmedNow) { /* folded above */ }
-            else if (hasObs && bothHalves) {
+            if (hasObs && bothHalves) {
               // the move was not accepted and both halves of the leaf-value table came with the verdict: nobody moves, one 16-byte read
               // per observation, the same two operations in the same order as below
 #pragma unroll
@@ -2052,7 +1884,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
           const int root = __builtin_amdgcn_readfirstlane(F.root), nb = doPropose ? __builtin_amdgcn_readfirstlane(F.nb) : 0, sset = __builtin_amdgcn_readfirstlane(F.sset);
           const bool bail = doPropose && __builtin_amdgcn_readfirstlane(F.needBig) != 0;
           bailNow = bail;
-          if (hasObs && !confirmedNow) {
+          if (hasObs) {
             // the B bins under the surviving proposal: the ones this thread routed a step ago when that very drawing of image 0 survived, else route now
             unsigned bb[SW_PF];
             const int set0 = 1 + sw_slot(t, 0);
@@ -2093,7 +1925,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
               for (int base = 0; base < nb; base += 8) {   // (8 bins per pass: sixteen accumulator pairs would not fit the registers beside the 16 observations)
                 if (base > 0) pass_barrier(bar);     // the reduction slots are free again
                 const int nbThis = nb - base < 8 ? nb - base : 8;
-                lastW = sweep_stats_n<8, FEW, false, false, BATCH>(nbThis, a, L, bar, O.r, lfCur, Ssel, bb, q0p, stride, nQuads, base, xCur, partOut, bail, pw, lnP, 0, nullptr, nullptr, nullptr, nullptr, jMax);
+                lastW = sweep_stats_n<8, FEW, false, false, BATCH>(nbThis, a, L, bar, O.r, lfCur, Ssel, bb, q0p, stride, nQuads, base, xCur, partOut, bail, pw, lnP, 0, nullptr, nullptr, jMax);
               }
             }
             // (the wave that published — the last of the four to arrive at the reduction — says so)
@@ -2144,7 +1976,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
             nbSpec = __builtin_amdgcn_readfirstlane(F.specNb[t & 1]);
           }
           SW_D(3);
-          run = S4B_LINEAR != 2 && nbSpec != 0 && idNext != 0 && nbNext >= 1 && nbNext <= 8;
+          run = nbSpec != 0 && idNext != 0 && nbNext >= 1 && nbNext <= 8;
         } else {
           run = run && nbNext >= 1 && nbNext <= 8;
           // (no barrier before the ahead pass: it uses neither the reduction slots nor anything another pass wave writes)
@@ -2163,7 +1995,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
           __builtin_amdgcn_s_setprio(S4B_PRIO_SPEC);
           if (pw == 1 && phase == 0) { SW_G(90); SW_W(9); }
           sweep_stats_n<8, FEW, true, false, BATCH>(nbNext, a, L, bar, O.r, lfNext, L.S + (1 + sw_slot(t + 1, 0)) * SW_NC, bbNext, q0p, stride, nQuads, 0, nullptr, nullptr, false, pw, lnP, 0,
-                                      &O.lfPrev, nullptr, nullptr, nullptr, jMax, &lfCur, L.ctab + (size_t)par1 * SW_CT_WORDS, L.preS + par1 * SW_PW * 8, foldD);
+                                      &O.lfPrev, nullptr, jMax, &lfCur, L.ctab + (size_t)par1 * SW_CT_WORDS, L.preS + par1 * SW_PW * 8, foldD);
           __builtin_amdgcn_s_setprio(0);
           ranAhead = true;
           if (phase == 0) { SW_D(4); }
@@ -2172,11 +2004,9 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
           // Everything the ahead pass leaves behind is in LDS, and a wave's LDS operations execute in the order it issued them: waiting for ITS OWN LDS counter orders its
           // pre-sums and counts before its arrival, and the last arriver's words before its flag.  (A release fence or store would also wait for the wave's outstanding
           // GLOBAL loads — the leaf ids requested a step ahead: 2 - 3 us of memory latency in front of wave 3's publish — measured, round 6.)
-#if S4B_X1
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
+          // The arrival is a release fence all the same: with the wait for the wave's LDS counter alone in its place (s_waitcnt lgkmcnt(0), built and measured in
+          // round 6) the chain differed from the oracle's in one run of four.
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-#endif
           // (two branches, not a pointer chosen by the phase)
           if (lnP == 0 && phase == 0) {
             if (__hip_atomic_fetch_add(&F.preArrA, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == SW_PW - 1) {
@@ -2204,21 +2034,11 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
       SW_MARK();
       if (ranAhead && nbSpec == 0) { SW_D(6); } else { SW_D0(); }      // (a step done the old way with its ahead pass behind it / the clock of the next step's first stamp)
       // (what this counter orders are this wave's LDS reads of the step: its own LDS counter, not a release — see the arrival above)
-#if S4B_X2
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (lane == 0) __hip_atomic_fetch_add(&F.passSeen, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-      if (lane == 0) __hip_atomic_fetch_add(&F.passSeen, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
     }
 #else
     SweepObs O;
-#if S4B_LFAHEAD
-    // Round 6: the leaf ids of tree t+1 are requested during step t, in front of the wait for wave 3's leaf values (a wait anyway: their 2 us of memory latency hide in
-    // it).  Requested at the top of their own step they stood in front of the routing — in the one window of a step that has no slack (measured with the linear
-    // statistics: 2.5 us from the end of a step to the first instruction of the next routing, 0.6 with the request a step ahead).
-    lfq_t lfN[SW_PF];
-#endif
     {
       SW_KERNARGS();
       const int64_t nQuads = (a.n + 3) >> 2;
@@ -2229,10 +2049,6 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
         if (hasObs && qd < nQuads) { const int64_t i0 = qd << 2; r01 = *reinterpret_cast<const double2*>(a.R + i0); r23 = *reinterpret_cast<const double2*>(a.R + i0 + 2); }
         O.r[j][0] = r01.x; O.r[j][1] = r01.y; O.r[j][2] = r23.x; O.r[j][3] = r23.y;
         O.lfPrev[j] = 0u; O.bbPrev[j] = 0xffffffffu;
-#if S4B_LFAHEAD
-        lfN[j] = 0u;
-        if (hasObs && qd < nQuads) lfN[j] = lfq_pack(__builtin_nontemporal_load(reinterpret_cast<const us4_t*>(a.leaf + (qd << 2))));
-#endif
       }
     }
     const int64_t q0w = q0;
@@ -2254,18 +2070,9 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
       // ---- the statistics half, as far as it does not depend on the pending decision: leaf ids of the observations in tree tn,
       // their A bins and leaf values, and their B bins under image 0 of the tree's proposal
       lfq_t lf[SW_PF]; unsigned bbI[1][SW_PF];
-      unsigned bitsQ[SW_PF]; bool preBits = false;      // (one byte of bin bits per observation under image 0, gathered behind the routing)
-#pragma unroll
-      for (int j = 0; j < SW_PF; ++j) bitsQ[j] = 0u;
       bool have0 = false;
 #pragma unroll
       for (int j = 0; j < SW_PF; ++j) { lf[j] = 0u; bbI[0][j] = 0xffffffffu; }
-#if S4B_LFAHEAD
-      if (doPropose && hasObs) {
-#pragma unroll
-        for (int j = 0; j < SW_PF; ++j) lf[j] = lfN[j];
-      }
-#else
       if (doPropose && hasObs) {
         const uint16_t* plane = a.leaf + (size_t)tn * a.npad;
 #pragma unroll
@@ -2274,7 +2081,6 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
           if (qd < nQuads) lf[j] = lfq_pack(__builtin_nontemporal_load(reinterpret_cast<const us4_t*>(plane + (qd << 2))));
         }
       }
-#endif
       // ---- wave 4: tree t+1, main arrays -> stage (the image waves propose for it during this step)
       if (pw == 0 && doPropose) {      // trees are staged two steps before they are decided (the image waves draw one step ahead)
         if (t == 0 && T > 1) stage_tree(a, L.stage, 1, lane);
@@ -2305,11 +2111,6 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
             sweep_route<1>(a, Ss, SPs, roots, haves, lf, q0, stride, nQuads, bb1);
 #pragma unroll
             for (int j = 0; j < SW_PF; ++j) bbI[0][j] = bb1[0][j];
-#if S4B_PREBITS
-            // (what the statistics of this step need of the tree and the proposal, gathered while this wave would only wait: see sweep_bits)
-            const int nbImg = S4B_UNI(c0.head->pr.nbA) + S4B_UNI(c0.head->pr.nbB);
-            if (!solo && nbImg >= 1 && nbImg <= 8) { sweep_bits<FEW>(a, lf, Ss[0], bbI[0], q0, stride, nQuads, pw, lane, jMax, bitsQ, L.redN + 64 + (t & 1) * 32); preBits = true; }
-#endif
           }
           if (pw == 0) SW_T(3);
           if (pw == 1) {  SW_AP(44); }
@@ -2333,19 +2134,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
       // same order as below: the same bits) and the step is over; otherwise the statistics are gathered again and go to the second ring,
       // where every workgroup — they all see the same verdict — then looks for the totals.
       const NodeA* const At = L.A + (t & 1) * SW_NC;      // leaf-value table of this step
-#if S4B_LFAHEAD
-      if (t + 1 < T && hasObs) {      // (tree t+1's plane is written — relabelling under an accepted move — two steps from now at the earliest)
-        const uint16_t* plane = a.leaf + (size_t)(t + 1) * a.npad;
-#pragma unroll
-        for (int j = 0; j < SW_PF; ++j) {
-          const int64_t qd = q0 + (int64_t)j * stride;
-          lfN[j] = 0u;
-          if (qd < nQuads) lfN[j] = lfq_pack(__builtin_nontemporal_load(reinterpret_cast<const us4_t*>(plane + (qd << 2))));
-        }
-      }
-#endif
       int nbSpec = 0;
-      double specS = 0.0; int specC = 0;      // (solo: the speculative totals, held by the reducing lanes of wave 4)
       if (doDecide && doPropose) {
         int guard = 0, sp;
         while (((sp = __hip_atomic_load(&F.specReady, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) >> 1) < t) {
@@ -2358,17 +2147,9 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
         if (nbSpec && hasObs) {
           __builtin_amdgcn_s_setprio(S4B_PRIO_SPEC);
           if (pw == 1) { SW_G(90); SW_W(9); }
-#if S4B_PREBITS
-          const bool lastS = preBits
-              ? sweep_stats_pre_n<FEW>(nbSpec, a, L, bar, O.r, lf, L.S + (1 + sw_slot(tn, 0)) * SW_NC, bitsQ, x.xbuf + (size_t)(t & (XC_RING - 1)) * XC_BUF_WORDS, pw, lane, O.lfPrev, At,
-                                       jMax, L.redN + 64 + (t & 1) * 32)
-              : sweep_stats_n<8, FEW, false, false, BATCH>(nbSpec, a, L, bar, O.r, lf, L.S + (1 + sw_slot(tn, 0)) * SW_NC, bbI[0], q0, stride, nQuads, 0,
-                           x.xbuf + (size_t)(t & (XC_RING - 1)) * XC_BUF_WORDS, nullptr, false, pw, lane, 0, &O.lfPrev, At, nullptr, nullptr, jMax);
-#else
           const bool lastS = sweep_stats_n<8, FEW, false, WT, BATCH>(nbSpec, a, L, bar, O.r, lf, L.S + (1 + sw_slot(tn, 0)) * SW_NC, bbI[0], q0, stride, nQuads, 0,
-                           x.xbuf + (size_t)(t & (XC_RING - 1)) * XC_BUF_WORDS, nullptr, false, pw, lane, 0, &O.lfPrev, At, solo ? &specS : nullptr, solo ? &specC : nullptr, jMax,
+                           x.xbuf + (size_t)(t & (XC_RING - 1)) * XC_BUF_WORDS, nullptr, false, pw, lane, 0, &O.lfPrev, At, jMax,
                            nullptr, nullptr, nullptr, nullptr, wLds + (size_t)pt * 4, nbSpec, x.wScale);
-#endif
           if (lastS) { if (lane == 0 && !solo) __hip_atomic_store(&F.published, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); SW_A(50); SW_G(91);
 #ifdef S4B_SWEEP_WG
             if (lane == 0 && t > 0 && t < T && (int)SW_BX < 256) {
@@ -2402,9 +2183,11 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
           spin_counter(&F.paGo, t + 1, &F.abort);
           if (__hip_atomic_load(&F.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
           if (sweep_spec_confirmed(F, t, nbSpec)) {
-            if (solo && pw == 0) {      // (one workgroup: the held sums are the totals of the next step — out first, the decider waits for nothing else)
+            // (unreachable: the exchange wave sets specNbPre, hence nbSpec, only `if (... && !solo)`.  Kept because removing it moves register allocation and scheduling all over
+            // k_sweep*, which needs a measured A/B of its own — DESIGN.md 5.0)
+            if (solo && pw == 0) {
               const int ln = sweep_fresh_lane();
-              if ((ln & 7) == 0 && (ln >> 3) < nbSpec) { bar.totS[ln >> 3] = specS; bar.totC[ln >> 3] = (double)specC; }
+              if ((ln & 7) == 0 && (ln >> 3) < nbSpec) { bar.totS[ln >> 3] = 0.0; bar.totC[ln >> 3] = 0.0; }
               if (ln == 0) __hip_atomic_store(&F.published, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
             if (hasObs) {
@@ -2538,7 +2321,7 @@ __device__ __forceinline__ void sweep_body(AK aKern, XK xKern) {      // (BATCH:
 #else
                              0,
 #endif
-                             nullptr, nullptr, nullptr, nullptr, jMax, nullptr, nullptr, nullptr, nullptr, wLds + (size_t)pt * 4, nb, x.wScale);
+                             nullptr, nullptr, jMax, nullptr, nullptr, nullptr, nullptr, wLds + (size_t)pt * 4, nb, x.wScale);
           }
         }
         if (lastW && lane == 0 && doPropose) __hip_atomic_store(nbSpec ? &F.publishedAlt : &F.published, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2667,12 +2450,12 @@ __global__ __launch_bounds__(FBLOCK) void k_sweep_stream(BartArrays aKern, Sweep
 // (cgm(split.probs): the same launches with the weighted predictor choice compiled into the wave-register control code — WaveModelT<true>, dev_control.hpp)
 __global__ __launch_bounds__(FBLOCK) void k_sweep_sp(BartArrays aKern, SweepArgs xKern) { sweep_body<false, false, true>(aKern, xKern); }
 __global__ __launch_bounds__(FBLOCK) void k_sweep_few_sp(BartArrays aKern, SweepArgs xKern) { sweep_body<false, true, true>(aKern, xKern); }
-#if !S4B_LINEAR && S4B_WAVERED
+#if !S4B_LINEAR
 // (observation weights: sweep_stats<.., WT>.  One kernel for every size: the instantiation without the skipped quads — three accumulators per bin unrolled over
 // four quads — spills 878 registers; the one with them, which the compiler does not interleave across the quads, none)
 __global__ __launch_bounds__(FBLOCK) void k_sweep_w(BartArrays aKern, SweepArgs xKern) { sweep_body<false, true, false, true>(aKern, xKern); }
 #else
-__global__ __launch_bounds__(FBLOCK) void k_sweep_w(BartArrays, SweepArgs xKern) { if (threadIdx.x == 0 && blockIdx.x == 0) *xKern.status = -3; }      // (the build variants with another reduction have no weighted sweep: refused, the host raises an error)
+__global__ __launch_bounds__(FBLOCK) void k_sweep_w(BartArrays, SweepArgs xKern) { if (threadIdx.x == 0 && blockIdx.x == 0) *xKern.status = -3; }      // (the linear variant has no weighted sweep: refused, the host raises an error)
 #endif
 // Batched launches of the solo sweep (the sweep group, dev_hip.hip): workgroup b is member b's one-workgroup sweep, its arguments in slot b.
 // No workgroup of such a launch waits for another one.
@@ -2680,10 +2463,10 @@ __global__ __launch_bounds__(FBLOCK) void k_sbatch(const unsigned char*) { sweep
 __global__ __launch_bounds__(FBLOCK) void k_sbatch_few(const unsigned char*) { sweep_body<false, true, false, false, true>(0, 0); }
 __global__ __launch_bounds__(FBLOCK) void k_sbatch_sp(const unsigned char*) { sweep_body<false, false, true, false, true>(0, 0); }
 __global__ __launch_bounds__(FBLOCK) void k_sbatch_few_sp(const unsigned char*) { sweep_body<false, true, true, false, true>(0, 0); }
-#if !S4B_LINEAR && S4B_WAVERED
+#if !S4B_LINEAR
 __global__ __launch_bounds__(FBLOCK) void k_sbatch_w(const unsigned char*) { sweep_body<false, true, false, true, true>(0, 0); }
 #else
-__global__ __launch_bounds__(FBLOCK) void k_sbatch_w(const unsigned char* slots) {      // (as k_sweep_w in these variants: refused; the host never batches a weighted member here)
+__global__ __launch_bounds__(FBLOCK) void k_sbatch_w(const unsigned char* slots) {      // (as k_sweep_w in the linear variant: refused; the host never batches a weighted member there)
   if (threadIdx.x == 0) *((const SweepArgs*)(slots + (size_t)blockIdx.x * SW_SLOT_BYTES + SW_SLOT_XOFF))->status = -3;
 }
 #endif

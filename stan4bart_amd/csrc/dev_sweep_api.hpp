@@ -20,9 +20,6 @@
 #ifndef S4B_LINEAR
 #define S4B_LINEAR 0
 #endif
-#ifndef S4B_WAVERED
-#define S4B_WAVERED 1      // the statistics' reduction: 1 per pass wave in registers, the last wave to arrive publishes (round 6); 0 the block reduction through LDS of round 5
-#endif
 
 namespace s4b {
 
@@ -62,7 +59,7 @@ __global__ __launch_bounds__(FBLOCK) void k_sbatch(const unsigned char* slots);
 __global__ __launch_bounds__(FBLOCK) void k_sbatch_few(const unsigned char* slots);
 __global__ __launch_bounds__(FBLOCK) void k_sbatch_sp(const unsigned char* slots);
 __global__ __launch_bounds__(FBLOCK) void k_sbatch_few_sp(const unsigned char* slots);
-__global__ __launch_bounds__(FBLOCK) void k_sbatch_w(const unsigned char* slots);      // (a stub in the build variants without k_sweep_w: never launched there)
+__global__ __launch_bounds__(FBLOCK) void k_sbatch_w(const unsigned char* slots);      // (a stub in the linear variant, which has no k_sweep_w: never launched there)
 // (measurement builds: each reads and clears)
 void sweep_timing_fetch(unsigned long long* out);
 void sweep_decide_fetch(unsigned long long* out);
