@@ -368,11 +368,13 @@ int S4B_FN(profile_leapfrog)(s4b_sampler* s, int32_t n_evals, double out[8]);
 int S4B_FN(set_test_hook)(s4b_sampler* s, int32_t hook, int64_t value);
 
 /* TEST ENTRY (no reference counterpart): ONE draw of the probit latents from the state as it stands, and nothing else of a sweep — the exact
- * draw of latent mode 0 (dbarts' sequential truncated normals from R's stream: k_latents2 + k_latents_finish on the device), then a wait and
- * the check of the device error word.  With set_state before it (r_rng, offset, total_fits, latents) and get_state after it, a test chooses the
- * 624 state words, mti, fits, offsets and previous latents the draw sees, which run() cannot offer: its tree sweep consumes a data-dependent
- * number of stream positions first.  Refused for a continuous response, in latent mode 1 and on a stored sampler.  Domain of the device draw:
- * an observation that needs more than 256 stream positions fails with "internal error" (DESIGN.md 5.4, 7). */
+ * draw of the sampler's latent mode, then a wait and the check of the device error word.  Mode 0: dbarts' sequential truncated normals from R's
+ * stream (k_latents2 + k_latents_finish on the device).  Mode 1: k_latents_par under the key and draw index of the state's tail; the draw index
+ * advances by one, R's stream stays.  With set_state before it (r_rng, offset, total_fits, latents; in mode 1 key and draw index) and get_state
+ * after it, a test chooses the 624 state words, mti, fits, offsets and previous latents the draw sees, which run() cannot offer: its tree sweep
+ * consumes a data-dependent number of stream positions first.  Refused for a continuous response and on a stored sampler.  Domain of the device
+ * draw, mode 0: an observation that needs more than 256 stream positions fails with "internal error" (DESIGN.md 5.4, 7); mode 1: a mean whose
+ * square overflows (|mean| above about 1.3e154) fails with "parallel latents: no proposal was accepted" (DESIGN.md 5.4b). */
 int S4B_FN(test_draw_latents)(s4b_sampler* s);
 
 /* TEST ENTRY (no reference counterpart): the Stan -> BART hand-off of ONE Gibbs iteration and nothing else — exactly what run() does between

@@ -539,8 +539,8 @@ class Sampler:
         self._check(self._f("set_test_hook")(self._h, int(hook), int(value)))
 
     def test_draw_latents(self):
-        """TEST ENTRY (include/stan4bart_amd.h): one exact draw of the probit latents from the current state (``set_state`` before, ``get_state``
-        after), nothing else of a sweep."""
+        """TEST ENTRY (include/stan4bart_amd.h): one draw of the probit latents from the current state (``set_state`` before, ``get_state``
+        after), nothing else of a sweep: the exact draw in latent mode 0, the parallel draw (key and draw index of the state's tail) in mode 1."""
         self._check(self._f("test_draw_latents")(self._h))
 
     def test_hand_off(self, beta, b, sigma: float, update_scale: bool):

@@ -38,21 +38,23 @@ S4B_PHX Philox4 philox4x32_10(Philox4 c, uint32_t k0, uint32_t k1) {
   }
   return c;
 }
-// a uniform on the open interval (0, 1) from two words: 53 bits, the midpoint of its cell (never 0, never 1), so that
+// a uniform on (0, 1] from two words: 53 bits m, (m + 1/2) 2^-53 formed in double — the midpoint of its cell below m = 2^52, rounded to even from
+// there on (the sum needs 54 bits), so never 0, and 1 for the one value m = 2^53 - 1 (log(1) = 0: rad = 0 or z = lower, both harmless) —, so that
 // -log(u) reaches 37.4 and the tails are not cut at 32-bit resolution
 S4B_PHX double philox_u53(uint32_t hi, uint32_t lo) {
   const uint64_t m = ((uint64_t)hi << 21) ^ (uint64_t)(lo >> 11);
   return ((double)m + 0.5) * 1.1102230246251565e-16;   // 2^-53
 }
 
-// every attempt is accepted with probability >= 0.75: 4 096 failures in a row only happen to a non-finite bound
+// every attempt is accepted with probability >= 0.75 while lower^2 is finite: 4 096 failures in a row only happen to a bound that is not finite
+// or whose square overflows (|lower| above sqrt(DBL_MAX), about 1.3e154: lam = inf and the acceptance probability is 0)
 constexpr int TN_MAX_ATTEMPTS = 1 << 12;
 // x ~ N(0, 1) | x >= lower, exactly, from the counters {draw, obs, attempt = 0, 1, ...}; one Philox block (two uniforms) per attempt.
 //   lower < 0:  normal rejection — the two Box-Muller deviates of the block are proposed in turn (acceptance >= 1 - 0.5^2 per attempt);
 //   lower >= 0: Robert's (1995) exponential proposal x = lower + E / lam, lam = (lower + sqrt(lower^2 + 4)) / 2, accepted with
 //               probability exp(-(x - lam)^2 / 2) (acceptance >= 0.76 per attempt, -> 1 as lower grows).
 // The switch at 0 is where the two cost about the same per accepted draw (and where dbarts switches).  Returns false (x = lower) when no
-// attempt was accepted: only a non-finite bound gets there.
+// attempt was accepted: only a bound that is not finite, or beyond about 1.3e154 on the exponential branch, gets there.
 S4B_PHX bool philox_trunc_normal(uint32_t k0, uint32_t k1, uint64_t draw, uint32_t obs, double lower, double& x) {
   Philox4 c = {{(uint32_t)draw, (uint32_t)(draw >> 32), obs, 0u}};
   if (lower < 0.0) {

@@ -674,11 +674,10 @@ class SamplerCore {
     if constexpr (kLatentMode) { dev_.set_latent_mode(mode, latKey_); latMode_ = mode; }
     else throw std::invalid_argument("this device layer has no parallel latent draw: latent mode 1 needs the HIP device layer");
   }
-  // TEST ENTRY (s4b_test_draw_latents): one exact latent draw from the state as it stands (set_state), nothing else of a sweep
+  // TEST ENTRY (s4b_test_draw_latents): one latent draw of the sampler's latent mode from the state as it stands (set_state), nothing else of a sweep
   void test_draw_latents() {
     live();
     if (!binary_) throw std::invalid_argument("test_draw_latents: this sampler's response is continuous (no probit latents)");
-    if (latMode_ != 0) throw std::invalid_argument("test_draw_latents: the sampler is in latent mode 1 (parallel); the entry draws the exact latents of mode 0");
     if constexpr (has_test_draw_latents<Dev>::value) { dev_.test_draw_latents(); check_device(); }
     else throw std::invalid_argument("test_draw_latents: this device layer has no latent draw on its own");
   }
@@ -999,7 +998,7 @@ class SamplerCore {
   void check_device() {
     int32_t e = dev_.error_flags();
     if (e & S4B_ERR_NODE_CAPACITY) throw std::runtime_error("a tree outgrew node_capacity; re-create the sampler with a larger bart_control.node_capacity");
-    if (e & S4B_ERR_I_LATENT) throw std::runtime_error("parallel latents: no proposal was accepted for an observation (a non-finite mean; device error word " + std::to_string(e) + ")");
+    if (e & S4B_ERR_I_LATENT) throw std::runtime_error("parallel latents: no proposal was accepted for an observation (a mean that is not finite or whose square overflows, |mean| above about 1.3e154; device error word " + std::to_string(e) + ")");
     if (e & S4B_ERR_INTERNAL) throw std::runtime_error("internal error: a hand-shake of the control kernel timed out, or one probit latent needed more than 256 positions of R's stream (device error word " + std::to_string(e) + ")");
     if (e & S4B_ERR_TRACE_OVERFLOW) throw std::runtime_error("trace buffer overflow: call get_trace more often");
   }

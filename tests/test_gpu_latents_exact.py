@@ -48,18 +48,12 @@ def test_kernel_matches_the_oracle_on_a_chosen_stream(oracle_lib, hip_lib, case)
 
 
 def test_the_entry_is_refused_where_it_does_not_apply(hip_lib):
-    """a continuous response has no latents; latent mode 1 draws them from another generator (tests/test_gpu_latents_parallel.py)."""
+    """a continuous response has no latents.  (In latent mode 1 the entry runs k_latents_par and is checked value by value:
+    tests/test_gpu_latents_par_alone.py.)"""
     from conftest import friedman_case
     s = make_sampler(hip_lib, "s4b_", friedman_case(n=60, T=3, warmup=2, iter=4)[0])
     try:
         with pytest.raises(RuntimeError, match="test_draw_latents"):
-            s.test_draw_latents()
-    finally:
-        s.free()
-    s = make_sampler(hip_lib, "s4b_", L.sampler_args(CASES[0]))
-    try:
-        s.set_latent_mode(1)
-        with pytest.raises(RuntimeError, match="latent mode 1"):
             s.test_draw_latents()
     finally:
         s.free()
