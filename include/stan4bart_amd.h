@@ -243,6 +243,43 @@ int S4B_FN(predict_bart)(s4b_sampler* s, const double* x_test, int64_t n_test, d
 /* the same with the reference's third argument: offset_test (n_test doubles, or NULL) is added to every draw's prediction */
 int S4B_FN(predict_bart_offset)(s4b_sampler* s, const double* x_test, int64_t n_test, const double* offset_test, double* out, int64_t* num_samples);
 
+/* extension (no reference counterpart; the reference forms these numbers in R from the full draws matrix of predictBART): SUMMARIES of the
+ * predictions of the kept draws at new rows, formed on the device without the n_test x num_samples matrix.  For row i and kept draw k
+ *     z(i,k) = bart(i,k) + offset[i] + sum_{j < n_dense} dense[i,j] dense_coef[k,j]                                   (j ascending)
+ *                                    + sum_{e < n_ell, ell_index[i,e] >= 0} ell_value[i,e] ell_coef[k, ell_index[i,e]]  (e ascending)
+ *     v(i,k) = z(i,k) (link 0) or Phi(z(i,k)), the standard normal cdf (link 1)
+ * with bart(i,k) exactly predict_bart's value (no rescale for a binary response: the latent scale).  Per row: mean[i] and
+ * m2[i] = sum_k (v(i,k) - mean[i])^2 over the draws (Welford's update in draw order; the variance is m2 / (num_samples - 1)).  Per draw:
+ * average[k,g] = sum_i weights[g,i] v(i,k) for n_weights <= 8 weight vectors, used as given (1 / n_test: the sample average; an indicator over
+ * its count: a subgroup's).  Two calls on one device return the same bits: no floating-point atomics, fixed orders.
+ * Layouts: x_test (n_test x p), dense (n_test x n_dense), ell_index and ell_value (n_test x n_ell) are column-major over the rows, as every matrix
+ * here; ell_index -1 marks padding (the entry is skipped), every other index lies in [0, n_ell_coef); the coefficient tables have ONE ROW PER DRAW:
+ * dense_coef[k * n_dense + j], ell_coef[k * n_ell_coef + c]; weights[g * n_test + i]; average is draw-major: average[k * n_weights + g].
+ * offset, dense*, ell_*, weights may be NULL when their count is 0 (offset: always).  Everything is checked before anything is launched.
+ * Works on a sampler with kept trees (keep_trees, sampling runs) and on a stored sampler.  out->mean = m2 = average = NULL (or in = NULL): only
+ * num_samples is set.  Device memory of a call: DESIGN.md 5.5 (no term grows with n_test x num_samples). */
+typedef struct {
+  const double* x_test; int64_t n_test;
+  const double* offset;          /* n_test or NULL */
+  int32_t n_dense, n_ell, n_ell_coef, link, n_weights;
+  int32_t route;                 /* 0 automatic; 1 the LDS-staged kernel where the largest kept draw fits its staging buffers, else global; 2 the global-memory walk */
+  int32_t stage_nodes;           /* 0, or an upper limit on the nodes per staging buffer below the library's own (less LDS per workgroup; a draw beyond it: global route) */
+  int32_t max_workgroups;        /* 0, or an upper limit on the workgroups below the library's own (bounds the scratch of the per-draw sums) */
+  const double* dense; const double* dense_coef;
+  const int32_t* ell_index; const double* ell_value; const double* ell_coef;
+  const double* weights;
+} s4b_summary_in;
+typedef struct {
+  double* mean; double* m2;      /* n_test each */
+  double* average;               /* num_samples x n_weights, draw-major; may be NULL when n_weights = 0 */
+  int64_t num_samples;
+  /* what the call did: [0] route taken (1 LDS-staged, 2 global; 0: nothing was launched), [1] rows per tile (= threads per workgroup), [2] workgroups,
+   * [3] staging bytes per buffer (nodes and tree starts; 0 on the global route), [4] nodes of the largest kept draw, [5] kernel launches,
+   * [6] bytes of device memory the call allocated, [7] nodes per staging buffer */
+  int64_t info[8];
+} s4b_summary_out;
+int S4B_FN(predict_summary)(s4b_sampler* s, const s4b_summary_in* in, s4b_summary_out* out);
+
 /* The state of a chain BETWEEN TWO GIBBS ITERATIONS as one relocatable byte string: what the next iteration starts from.  It is
  * the hook of the teacher-forced parity tests (state of one implementation injected into the other before every compared
  * transition) and lets a chain continue in another sampler created from the same data; it is not an archive of a fit: the

@@ -83,6 +83,22 @@ class Results(C.Structure):
                 ("bart_test", c_double_p), ("bart_varcount", c_int32_p), ("bart_k", c_double_p)]
 
 
+class SummaryIn(C.Structure):          # s4b_summary_in
+    _fields_ = [("x_test", c_double_p), ("n_test", C.c_int64), ("offset", c_double_p),
+                ("n_dense", C.c_int32), ("n_ell", C.c_int32), ("n_ell_coef", C.c_int32), ("link", C.c_int32), ("n_weights", C.c_int32),
+                ("route", C.c_int32), ("stage_nodes", C.c_int32), ("max_workgroups", C.c_int32),
+                ("dense", c_double_p), ("dense_coef", c_double_p), ("ell_index", c_int32_p), ("ell_value", c_double_p), ("ell_coef", c_double_p),
+                ("weights", c_double_p)]
+
+
+class SummaryOut(C.Structure):         # s4b_summary_out
+    _fields_ = [("mean", c_double_p), ("m2", c_double_p), ("average", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
+SUMMARY_ROUTES = {"auto": 0, "staged": 1, "global": 2}
+SUMMARY_INFO = ("route", "rows_per_tile", "workgroups", "staging_bytes", "largest_draw_nodes", "launches", "device_bytes", "staging_nodes")
+
+
 def _dp(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(c_double_p)
 
@@ -303,6 +319,7 @@ class Sampler:
             "profile_sweep": [vp, i32, dp], "profile_leapfrog": [vp, i32, dp],
             "set_progress": [vp, PROGRESS, vp], "set_device_sharing": [vp, i32],
             "set_tree_path": [vp, i32], "get_tree_path": [vp, ip], "get_fused_stats": [vp, C.POINTER(i64)], "get_sweep_stats": [vp, C.POINTER(i64)], "get_sweep_busy": [vp, C.POINTER(i64)], "get_sweep_spec": [vp, C.POINTER(i64)], "set_test_hook": [vp, i32, i64], "set_hmc_mode": [vp, i32], "get_hmc_mode": [vp, ip],
+            "predict_summary": [vp, C.POINTER(SummaryIn), C.POINTER(SummaryOut)],
             "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
         }
         for name, argtypes in sig.items():
@@ -599,6 +616,66 @@ class Sampler:
                 self._check(self._f("predict_bart")(self._h, _dp(xt), xt.shape[0], _dp(out), C.byref(ns)))
         return out
 
+    def predict_summary(self, x_test: np.ndarray, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None, ell_coef=None,
+                        link: int = 0, weights=None, route="auto", stage_nodes: int = 0, max_workgroups: int = 0) -> dict:
+        """``s4b_predict_summary``: summaries of the kept draws' predictions at new rows, formed on the device without the [rows x draws] matrix.
+        For row i and draw k, z = bart + offset[i] + dense[i] . dense_coef[k] + sum_e ell_value[i, e] * ell_coef[k, ell_index[i, e]] (index -1:
+        padding), v = z (link 0) or Phi(z) (link 1).  dense [rows x M], dense_coef [draws x M], ell_index / ell_value [rows x E], ell_coef
+        [draws x q], weights [G x rows] with G <= 8.  Returns dict(mean [rows], m2 [rows] = sum_k (v - mean)^2, average [draws x G] = weights @ v,
+        draws, info: what the call did, SUMMARY_INFO)."""
+        fn = getattr(self._lib, self._pfx + "predict_summary", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_summary")
+        xt = _f64(x_test)
+        if xt.ndim != 2:
+            raise ValueError("x_test must be a matrix [rows x predictors]")
+        rows = xt.shape[0]
+        probe = SummaryOut()
+        self._check(fn(self._h, None, C.byref(probe)))
+        S = int(probe.num_samples)
+
+        def table(a, first, what):
+            if a is None:
+                return None, 0
+            a = np.asarray(a)
+            if a.ndim != 2 or a.shape[0] != first:
+                raise ValueError(f"{what} must have {first} rows, not shape {a.shape}")
+            return a, a.shape[1]
+        dense, M = table(dense, rows, "dense")
+        dense_coef, Mc = table(dense_coef, S, "dense_coef")
+        ell_index, E = table(ell_index, rows, "ell_index")
+        ell_value, Ev = table(ell_value, rows, "ell_value")
+        ell_coef, q = table(ell_coef, S, "ell_coef")
+        if M != Mc:
+            raise ValueError(f"dense has {M} columns, dense_coef {Mc}")
+        if E != Ev:
+            raise ValueError(f"ell_index has {E} columns, ell_value {Ev}")
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.ndim != 2 or weights.shape[1] != rows:
+                raise ValueError(f"weights must be [G x {rows}], not shape {weights.shape}")
+        G = 0 if weights is None else weights.shape[0]
+        off = None
+        if offset is not None:
+            off = _f64(offset)
+            if off.shape != (rows,):
+                raise ValueError("length of offset must equal number of rows in x_test")
+        keep = dict(dense=None if not M else _f64(dense), dense_coef=None if not M else _f64(dense_coef, "C"),
+                    ell_index=None if not E else np.asfortranarray(np.asarray(ell_index, dtype=np.int32)),
+                    ell_value=None if not E else _f64(ell_value), ell_coef=None if not E else _f64(ell_coef, "C"),
+                    weights=None if not G else _f64(weights, "C"))
+        mean, m2, avg = np.zeros(rows), np.zeros(rows), np.zeros((S, G))
+        arg = SummaryIn(x_test=_dp(xt), n_test=rows, offset=_dp(off), n_dense=M, n_ell=E, n_ell_coef=q if E else 0, link=int(link), n_weights=G,
+                        route=int(SUMMARY_ROUTES.get(route, route)), stage_nodes=int(stage_nodes), max_workgroups=int(max_workgroups),
+                        dense=_dp(keep["dense"]), dense_coef=_dp(keep["dense_coef"]), ell_index=_ip(keep["ell_index"]),
+                        ell_value=_dp(keep["ell_value"]), ell_coef=_dp(keep["ell_coef"]), weights=_dp(keep["weights"]))
+        out = SummaryOut(mean=_dp(mean), m2=_dp(m2), average=_dp(avg) if avg.size else None)
+        self.summary_info = dict(zip(SUMMARY_INFO, [0] * 8))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        self.summary_info = dict(zip(SUMMARY_INFO, (int(v) for v in out.info)))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        return dict(mean=mean, m2=m2, average=avg, draws=int(out.num_samples), info=dict(self.summary_info))
+
     def profile_leapfrog(self, n_evals: int = 10) -> dict:
         """Per-leapfrog O(N) sums of the hmc_mode 1 path timed with HIP events (measurement hook of the HIP library)."""
         out = (C.c_double * 8)()
@@ -714,6 +791,7 @@ class StoredSampler:
     _f = Sampler._f
     _check = Sampler._check
     predict_bart = Sampler.predict_bart
+    predict_summary = Sampler.predict_summary
     export_bart_state = Sampler.export_bart_state
     get_kept_trees = Sampler.get_kept_trees
     get_kept_trees_indexed = Sampler.get_kept_trees_indexed

@@ -59,6 +59,18 @@ template <class D> struct has_latent_mode<D, std::void_t<decltype(&D::set_latent
 template <class D, class = void> struct has_test_draw_latents : std::false_type {};
 template <class D> struct has_test_draw_latents<D, std::void_t<decltype(&D::test_draw_latents)>> : std::true_type {};
 
+// does the device layer summarise the stored-tree predictions on the device (s4b_predict_summary)?  A layer without it still builds; the entry is refused there.
+template <class D, class = void> struct has_predict_summary : std::false_type {};
+template <class D> struct has_predict_summary<D, std::void_t<decltype(&D::predict_summary)>> : std::true_type {};
+// one s4b_predict_summary call as the device layer sees it: host pointers, the new rows binned, the kept trees, the validated arguments
+struct SummaryCall {
+  const uint16_t* xb; int64_t nT; const PackedNode* nodes; size_t numNodes; const int64_t* treeStart; int64_t S; int T; const double* scale; int binary;
+  int64_t maxDrawNodes;          // nodes of the largest kept draw: the route is chosen from it
+  const double* offset; int M; const double* dense; const double* denseCoef; int E, q; const int32_t* ellIndex; const double* ellValue; const double* ellCoef;
+  int link, G; const double* weights; int route, stageNodes, maxWorkgroups;
+  double* mean; double* m2; double* average; int64_t* info;
+};
+
 template <class Dev>
 class SamplerCore {
  public:
@@ -501,6 +513,49 @@ class SamplerCore {
     // offset_test of stan4bart_predictBART (reference src/init.cpp:377-384): added to every draw's prediction
     if (offsetTest) for (int64_t k = 0; k < S; ++k) for (int64_t i = 0; i < nT; ++i) out[(size_t)k * (size_t)nT + (size_t)i] += offsetTest[i];
     return S;
+  }
+  // s4b_predict_summary: per-row mean / m2 over the kept draws and per-draw weighted row sums of bart + offset + dense + ELL parts (link 0 / 1),
+  // formed on the device without the [rows x draws] matrix.  Everything is validated here, before any launch.  Live (kept trees) and stored samplers.
+  int64_t predict_summary(const s4b_summary_in* in, s4b_summary_out* out) {
+    if (!out) throw std::invalid_argument("predict_summary: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t S = (int64_t)keptScale_.size() / 2;
+    out->num_samples = S;
+    if (!in || (!out->mean && !out->m2 && !out->average)) return S;          // query
+    if constexpr (has_predict_summary<Dev>::value) {
+      const int64_t nT = in->n_test;
+      if (nT < 1 || !in->x_test) throw std::invalid_argument("predict_summary: x_test must have at least one row");
+      if (in->n_weights < 0 || in->n_weights > 8) throw std::invalid_argument("predict_summary: between 0 and 8 weight vectors, not " + std::to_string(in->n_weights));
+      if (in->link != 0 && in->link != 1) throw std::invalid_argument("predict_summary: link must be 0 (identity) or 1 (standard normal cdf)");
+      if (in->n_dense < 0 || in->n_ell < 0) throw std::invalid_argument("predict_summary: negative n_dense or n_ell");
+      if (in->n_dense > 0 && (!in->dense || !in->dense_coef)) throw std::invalid_argument("predict_summary: n_dense > 0 needs dense and dense_coef");
+      if (in->n_ell > 0 && (!in->ell_index || !in->ell_value || !in->ell_coef || in->n_ell_coef < 1))
+        throw std::invalid_argument("predict_summary: n_ell > 0 needs ell_index, ell_value, ell_coef and n_ell_coef >= 1");
+      if (in->n_weights > 0 && !in->weights) throw std::invalid_argument("predict_summary: n_weights > 0 needs weights");
+      if (in->route < 0 || in->route > 2) throw std::invalid_argument("predict_summary: route must be 0 (automatic), 1 (staged) or 2 (global)");
+      if (in->stage_nodes < 0 || in->max_workgroups < 0) throw std::invalid_argument("predict_summary: negative stage_nodes or max_workgroups");
+      if (!out->mean || !out->m2 || (in->n_weights > 0 && !out->average)) throw std::invalid_argument("predict_summary: mean, m2 and (with weights) average must all be given");
+      for (size_t x = 0, m = (size_t)nT * (size_t)in->n_ell; x < m; ++x)
+        if (in->ell_index[x] < -1 || in->ell_index[x] >= in->n_ell_coef)
+          throw std::invalid_argument("predict_summary: ell_index " + std::to_string(in->ell_index[x]) + " outside [-1, " + std::to_string(in->n_ell_coef) + ")");
+      if (S == 0) throw std::invalid_argument("predict_summary: the sampler holds no kept draws (bart_control.keep_trees, sampling runs)");
+      std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
+      bin_matrix(in->x_test, (size_t)nT, xb);
+      int64_t largest = 0;
+      for (int64_t k = 0; k < S; ++k) {
+        const int64_t en = k + 1 < S ? keptTreeStart_[(size_t)((k + 1) * T_)] : (int64_t)keptNodes_.size();
+        largest = std::max(largest, en - keptTreeStart_[(size_t)(k * T_)]);
+      }
+      SummaryCall c{};
+      c.xb = xb.data(); c.nT = nT; c.nodes = keptNodes_.data(); c.numNodes = keptNodes_.size(); c.treeStart = keptTreeStart_.data(); c.S = S; c.T = T_;
+      c.scale = keptScale_.data(); c.binary = binary_ ? 1 : 0; c.maxDrawNodes = largest;
+      c.offset = in->offset; c.M = in->n_dense; c.dense = in->dense; c.denseCoef = in->dense_coef;
+      c.E = in->n_ell; c.q = in->n_ell_coef; c.ellIndex = in->ell_index; c.ellValue = in->ell_value; c.ellCoef = in->ell_coef;
+      c.link = in->link; c.G = in->n_weights; c.weights = in->weights; c.route = in->route; c.stageNodes = in->stage_nodes; c.maxWorkgroups = in->max_workgroups;
+      c.mean = out->mean; c.m2 = out->m2; c.average = out->average; c.info = out->info;
+      dev_.predict_summary(c);
+      return S;
+    } else throw std::invalid_argument("predict_summary: this device layer has no summary kernel (the summaries are formed by the HIP library only)");
   }
   // ---- sampler state as a byte string (layout: include/stan4bart_amd.h, s4b_get_state)
   int64_t get_state(void* buf, int64_t cap) {

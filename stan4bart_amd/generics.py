@@ -313,6 +313,116 @@ class Stan4bartFit:
                 result = result + rng.standard_normal(result.shape) * sig[None]
         return combine_chains_f(result) if combine_chains else result
 
+    # ------------------------------------------------------------------ predict_summary
+    def _ell_random(self, terms_new, sample_new_levels, rng):
+        """The random part of ``_fitted_random`` as an ELL table over the rows: (ell_index [n x E] int32, ell_value [n x E], coefficient tables
+        [chain][draws x q']).  One entry per term and slope (E = sum of the terms' p): its column is the coefficient's position in the chain's ``b``
+        table (level-major, the p coefficients of a level adjacent); unseen levels are appended as extra columns and drawn per draw exactly as
+        ``_fitted_random`` draws them (the same generator calls in the same order); with ``sample_new_levels=False`` their entries are padding
+        (index -1: they contribute nothing)."""
+        stan = self._get("stan", False, False)
+        b_all = stan[self._rows("b.")]                               # [q, iter, chain]
+        q, n_iter, n_chain = b_all.shape
+        names = {g.name: g for g in self.terms}
+        base, at = {}, 0
+        for g in self.terms:
+            base[g.name] = at
+            at += g.p * g.l
+        n = len(terms_new[0].levels)
+        idx_cols, val_cols, extra = [], [], []                       # extra: [p * n_new, iter, chain] blocks appended after the q columns
+        n_extra, Sig = 0, None
+        for g in terms_new:
+            if g.name not in names:
+                raise ValueError("grouping factors specified that were not present in original model")
+            old = names[g.name]
+            if g.p != old.p:
+                raise ValueError("random effects specified that were not present in original model")
+            lev = np.asarray(g.levels, dtype=np.int64)
+            n_new = int(max(0, lev.max() - old.l))
+            seen = lev <= old.l
+            col0 = np.where(seen, base[g.name] + (lev - 1) * g.p, -1)
+            if n_new:
+                if sample_new_levels:
+                    Sig = Sig or self._sigma_arrays(False, False)
+                    S = Sig[g.name]
+                    ext = np.zeros((g.p, n_new, n_iter, n_chain))
+                    for i in range(n_iter):
+                        for c in range(n_chain):
+                            L = np.linalg.cholesky(S[:, :, i, c] + 1e-300 * np.eye(g.p))
+                            ext[:, :, i, c] = L @ rng.standard_normal((g.p, n_new))
+                    extra.append(ext.transpose(1, 0, 2, 3).reshape(n_new * g.p, n_iter, n_chain))      # level-major, like b
+                    col0 = np.where(seen, col0, q + n_extra + (lev - old.l - 1) * g.p)
+                    n_extra += n_new * g.p
+            vals = np.ones((n, g.p))
+            if g.p > 1:
+                vals[:, 1:] = np.asarray(g.slopes, dtype=np.float64).reshape(n, g.p - 1)
+            for j in range(g.p):
+                idx_cols.append(np.where(col0 >= 0, col0 + j, -1))
+                val_cols.append(vals[:, j])
+        table = np.concatenate([b_all] + extra, axis=0) if extra else b_all
+        coef = [np.ascontiguousarray(table[:, :, c].T) for c in range(n_chain)]
+        return np.column_stack(idx_cols).astype(np.int32), np.column_stack(val_cols), coef
+
+    @staticmethod
+    def _pool_chains(parts):
+        """(count, mean, m2) of several chains pooled pairwise (Chan et al.): O(rows x chains)."""
+        n, mean, m2 = parts[0]
+        mean, m2 = mean.copy(), m2.copy()
+        for nb, mb, m2b in parts[1:]:
+            d = mb - mean
+            tot = n + nb
+            mean = mean + d * (nb / tot)
+            m2 = m2 + m2b + d * d * (n * nb / tot)
+            n = tot
+        return n, mean, m2
+
+    def predict_summary(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, type: str = "ev", row_weights=None,
+                        combine_chains: bool = True, sample_new_levels: bool = True, seed: Optional[int] = None):
+        """What users take from ``predict``'s [rows x draws] matrix, formed on the device without it (``s4b_predict_summary``, one call per chain):
+        ``mean`` and ``sd`` (ddof 1) per row over all draws and chains, and ``average`` [G, iter, chain] — per draw, ``row_weights`` [G x rows]
+        (G <= 8, used as given; None: one vector of 1 / rows, the sample average) applied to the rows: sample and subgroup average effects.
+        ``type`` "ev" or "indiv.bart"; for a given ``seed`` the draws of unseen levels are ``predict``'s.  Needs bart_args keepTrees."""
+        if type == "ppd":
+            raise ValueError("predict_summary does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("predict_summary requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_summary needs x_bart, the new rows of the BART predictors")
+        x_bart = np.asarray(x_bart, dtype=np.float64)
+        rows = x_bart.shape[0]
+        if row_weights is None:
+            w = np.full((1, rows), 1.0 / rows)
+        else:
+            w = np.asarray(row_weights, dtype=np.float64)
+            if w.ndim != 2 or w.shape[1] != rows:
+                raise ValueError(f"row_weights must have shape [G, {rows}], not {w.shape}")
+            if not 1 <= w.shape[0] <= 8:
+                raise ValueError(f"row_weights holds {w.shape[0]} weight vectors: between 1 and 8 per call")
+        rng = np.random.default_rng(seed)
+        ev = type == "ev"
+        n_fixef, n_terms, n_chain = len(self._rows("beta.")), len(self.terms), len(self.samplers)
+        dense = dense_coef = ell_index = ell_value = ell_coef = None
+        if ev and X is not None and n_fixef:
+            beta = self.stan[self._rows("beta.")]                    # [K, iter, chain]
+            dense = np.asarray(X, dtype=np.float64).reshape(-1, n_fixef) - self.X_means
+            dense_coef = [np.ascontiguousarray(beta[:, :, c].T) for c in range(n_chain)]
+        if ev and groups is not None and len(groups) and n_terms:
+            order = {g.name: g for g in groups}
+            ell_index, ell_value, ell_coef = self._ell_random([order[g.name] for g in self.terms if g.name in order], sample_new_levels, rng)
+        parts, avgs = [], []
+        for c, smp in enumerate(self.samplers):
+            r = smp.predict_summary(x_bart, offset=offset if ev else None, dense=dense, dense_coef=None if dense is None else dense_coef[c],
+                                    ell_index=ell_index, ell_value=ell_value, ell_coef=None if ell_index is None else ell_coef[c],
+                                    link=1 if (ev and self.family == "binomial") else 0, weights=w)
+            parts.append((r["draws"], r["mean"], r["m2"]))
+            avgs.append(r["average"].T)                              # [G, iter]
+        n, mean, m2 = self._pool_chains(parts)
+        sd = np.sqrt(m2 / (n - 1)) if n > 1 else np.full(rows, np.nan)
+        average = np.stack(avgs, axis=2)
+        return {"mean": mean, "sd": sd, "draws": int(n), "average": combine_chains_f(average) if combine_chains else average}
+
     def export_bart_states(self) -> list:
         """``stan4bart_exportBARTState`` per chain (reference R/stan4bart_fit.R:572-580): byte strings that
         ``attach_stored_samplers`` turns back into predict-capable samplers, in this or another process."""
