@@ -280,6 +280,32 @@ typedef struct {
 } s4b_summary_out;
 int S4B_FN(predict_summary)(s4b_sampler* s, const s4b_summary_in* in, s4b_summary_out* out);
 
+/* extension (dbarts' pdbart / pd2bart, formed on the device): the PARTIAL DEPENDENCE of the kept draws on one or two BART predictors.  For grid point g,
+ * which assigns grid[g + w * n_grid] to predictor vars[w] (w < n_vars; two predictors: a joint grid, the caller lists the pairs), and kept draw k
+ *     pd[k * n_grid + g] = sum_i weight[i] * v(i, g, k),     v = z (link 0) or Phi(z) (link 1),
+ *     z(i, g, k) = bart(row i with x[vars[w]] replaced by the grid point's values; draw k) + the linear parts of predict_summary at row i, draw k
+ * in ONE call that walks the trees without a rule on a varied predictor once per (row, draw) and only the others per grid point.
+ * THE VARIED PREDICTORS ARE BART PREDICTORS ONLY: offset, dense and ELL parts stay at the rows' own values, whatever the grid.  `rows` is
+ * predict_summary's input with n_weights 0 (weight 1 / n_test: the sample average) or 1 (weights[i]); route, stage_nodes and max_workgroups mean what
+ * they mean there.  The grid is binned as rows are (+-inf allowed: the ends; a NaN is refused).  There are no per-row outputs: the individual curves
+ * are predict_summary's mean per grid value.  The trees of a draw are added in another order than predict_bart adds them, so the BART term agrees with
+ * it to rounding, not bit for bit; two calls, both routes, live and stored samplers return the same bits.  Everything is checked before anything is
+ * launched.  out->pd = NULL (or in = NULL): only num_samples is set. */
+typedef struct {
+  s4b_summary_in rows;
+  int32_t n_vars, vars[2], n_grid;   /* 1 or 2 distinct predictors in [0, p); 1 <= n_grid <= 64 */
+  const double* grid;                /* n_grid x n_vars, column-major */
+} s4b_pd_in;
+typedef struct {
+  double* pd;                        /* num_samples x n_grid, draw-major */
+  int64_t num_samples;
+  /* as s4b_summary_out.info, except: [3] staging bytes per buffer (nodes, tree starts and the tree order: 16 x nodes + 8 x trees), [4] nodes of the
+   * largest kept draw (the staged route needs them in one buffer, with 16 KB of reduction space and both order tables inside the 160 KB of LDS),
+   * [7] the trees with a rule on a varied predictor: (the most in one draw) << 32 | (their sum over the draws) */
+  int64_t info[8];
+} s4b_pd_out;
+int S4B_FN(partial_dependence)(s4b_sampler* s, const s4b_pd_in* in, s4b_pd_out* out);
+
 /* The state of a chain BETWEEN TWO GIBBS ITERATIONS as one relocatable byte string: what the next iteration starts from.  It is
  * the hook of the teacher-forced parity tests (state of one implementation injected into the other before every compared
  * transition) and lets a chain continue in another sampler created from the same data; it is not an archive of a fit: the

@@ -95,8 +95,18 @@ class SummaryOut(C.Structure):         # s4b_summary_out
     _fields_ = [("mean", c_double_p), ("m2", c_double_p), ("average", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
 
 
+class PdIn(C.Structure):               # s4b_pd_in
+    _fields_ = [("rows", SummaryIn), ("n_vars", C.c_int32), ("vars", C.c_int32 * 2), ("n_grid", C.c_int32), ("grid", c_double_p)]
+
+
+class PdOut(C.Structure):              # s4b_pd_out
+    _fields_ = [("pd", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
 SUMMARY_ROUTES = {"auto": 0, "staged": 1, "global": 2}
 SUMMARY_INFO = ("route", "rows_per_tile", "workgroups", "staging_bytes", "largest_draw_nodes", "launches", "device_bytes", "staging_nodes")
+PD_INFO = SUMMARY_INFO[:7] + ("largest_affected", "total_affected")          # (the last two share info[7]: trees with a rule on a varied predictor)
+PD_GRID_MAX = 64                       # grid points per s4b_partial_dependence call
 
 
 def _dp(a: Optional[np.ndarray]):
@@ -320,6 +330,7 @@ class Sampler:
             "set_progress": [vp, PROGRESS, vp], "set_device_sharing": [vp, i32],
             "set_tree_path": [vp, i32], "get_tree_path": [vp, ip], "get_fused_stats": [vp, C.POINTER(i64)], "get_sweep_stats": [vp, C.POINTER(i64)], "get_sweep_busy": [vp, C.POINTER(i64)], "get_sweep_spec": [vp, C.POINTER(i64)], "set_test_hook": [vp, i32, i64], "set_hmc_mode": [vp, i32], "get_hmc_mode": [vp, ip],
             "predict_summary": [vp, C.POINTER(SummaryIn), C.POINTER(SummaryOut)],
+            "partial_dependence": [vp, C.POINTER(PdIn), C.POINTER(PdOut)],
             "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
         }
         for name, argtypes in sig.items():
@@ -626,13 +637,26 @@ class Sampler:
         fn = getattr(self._lib, self._pfx + "predict_summary", None)
         if fn is None:
             raise RuntimeError(f"this library ({self._pfx}*) has no predict_summary")
+        probe = SummaryOut()
+        self._check(fn(self._h, None, C.byref(probe)))
+        S = int(probe.num_samples)
+        arg, keep, rows, G = self._summary_in(S, x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, weights, route, stage_nodes,
+                                              max_workgroups)
+        mean, m2, avg = np.zeros(rows), np.zeros(rows), np.zeros((S, G))
+        out = SummaryOut(mean=_dp(mean), m2=_dp(m2), average=_dp(avg) if avg.size else None)
+        self.summary_info = dict(zip(SUMMARY_INFO, [0] * 8))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        self.summary_info = dict(zip(SUMMARY_INFO, (int(v) for v in out.info)))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        return dict(mean=mean, m2=m2, average=avg, draws=int(out.num_samples), info=dict(self.summary_info))
+
+    @staticmethod
+    def _summary_in(S, x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, weights, route, stage_nodes, max_workgroups):
+        """The ``s4b_summary_in`` of a call on a sampler with S kept draws: (struct, the arrays it points into, rows, weight vectors)."""
         xt = _f64(x_test)
         if xt.ndim != 2:
             raise ValueError("x_test must be a matrix [rows x predictors]")
         rows = xt.shape[0]
-        probe = SummaryOut()
-        self._check(fn(self._h, None, C.byref(probe)))
-        S = int(probe.num_samples)
 
         def table(a, first, what):
             if a is None:
@@ -664,17 +688,51 @@ class Sampler:
                     ell_index=None if not E else np.asfortranarray(np.asarray(ell_index, dtype=np.int32)),
                     ell_value=None if not E else _f64(ell_value), ell_coef=None if not E else _f64(ell_coef, "C"),
                     weights=None if not G else _f64(weights, "C"))
-        mean, m2, avg = np.zeros(rows), np.zeros(rows), np.zeros((S, G))
+        keep.update(x_test=xt, offset=off)
         arg = SummaryIn(x_test=_dp(xt), n_test=rows, offset=_dp(off), n_dense=M, n_ell=E, n_ell_coef=q if E else 0, link=int(link), n_weights=G,
                         route=int(SUMMARY_ROUTES.get(route, route)), stage_nodes=int(stage_nodes), max_workgroups=int(max_workgroups),
                         dense=_dp(keep["dense"]), dense_coef=_dp(keep["dense_coef"]), ell_index=_ip(keep["ell_index"]),
                         ell_value=_dp(keep["ell_value"]), ell_coef=_dp(keep["ell_coef"]), weights=_dp(keep["weights"]))
-        out = SummaryOut(mean=_dp(mean), m2=_dp(m2), average=_dp(avg) if avg.size else None)
-        self.summary_info = dict(zip(SUMMARY_INFO, [0] * 8))
+        return arg, keep, rows, G
+
+    def partial_dependence(self, x_test: np.ndarray, vars, grid, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None,
+                           ell_coef=None, link: int = 0, weights=None, route="auto", stage_nodes: int = 0, max_workgroups: int = 0) -> dict:
+        """``s4b_partial_dependence``: for every kept draw and every grid point the weighted row sum of the prediction with the BART predictors ``vars``
+        (one index or two) set to the grid point's values, in one fused device call.  ``grid`` [G] or [G x len(vars)], G <= 64 (two predictors: the
+        pairs of a joint grid, listed by the caller); ``weights`` None (1 / rows: the sample average) or [rows]; the other arguments as
+        ``predict_summary`` takes them — the linear parts stay at the rows' own values.  Returns dict(pd [draws x G], draws, info: PD_INFO)."""
+        fn = getattr(self._lib, self._pfx + "partial_dependence", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no partial_dependence")
+        probe = PdOut()
+        self._check(fn(self._h, None, C.byref(probe)))
+        S = int(probe.num_samples)
+        vs = np.atleast_1d(np.asarray(vars, dtype=np.int64))
+        if vs.ndim != 1 or len(vs) not in (1, 2):
+            raise ValueError(f"vars must be one predictor index or two, not {vars!r}")
+        gr = np.asarray(grid, dtype=np.float64)
+        if gr.ndim == 1:
+            gr = gr[:, None]
+        if gr.ndim != 2 or gr.shape[1] != len(vs):
+            raise ValueError(f"grid must be [G] or [G x {len(vs)}], not shape {np.shape(grid)}")
+        gr = np.asfortranarray(gr)
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.ndim == 1:
+                weights = weights[None, :]
+        rows_in, keep, rows, _ = self._summary_in(S, x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, weights, route,
+                                                   stage_nodes, max_workgroups)
+        pd = np.zeros((S, gr.shape[0]))
+        arg = PdIn(rows=rows_in, n_vars=len(vs), vars=(C.c_int32 * 2)(int(vs[0]), int(vs[-1]) if len(vs) > 1 else -1), n_grid=gr.shape[0], grid=_dp(gr))
+        buf = pd if pd.size else np.zeros(1)          # (no draws or no grid point: refused by the library, which needs a pointer to tell the call from a query)
+        out = PdOut(pd=_dp(buf))
+        self.pd_info = dict(zip(PD_INFO, [0] * 9))
         rc = fn(self._h, C.byref(arg), C.byref(out))
-        self.summary_info = dict(zip(SUMMARY_INFO, (int(v) for v in out.info)))          # (all zero after a refusal: nothing was launched)
+        w = [int(v) for v in out.info]
+        self.pd_info = dict(zip(PD_INFO, w[:7] + [w[7] >> 32, w[7] & 0xFFFFFFFF]))          # (all zero after a refusal: nothing was launched)
         self._check(rc)
-        return dict(mean=mean, m2=m2, average=avg, draws=int(out.num_samples), info=dict(self.summary_info))
+        del keep, buf
+        return dict(pd=pd, draws=int(out.num_samples), info=dict(self.pd_info))
 
     def profile_leapfrog(self, n_evals: int = 10) -> dict:
         """Per-leapfrog O(N) sums of the hmc_mode 1 path timed with HIP events (measurement hook of the HIP library)."""
@@ -792,6 +850,8 @@ class StoredSampler:
     _check = Sampler._check
     predict_bart = Sampler.predict_bart
     predict_summary = Sampler.predict_summary
+    _summary_in = staticmethod(Sampler._summary_in)
+    partial_dependence = Sampler.partial_dependence
     export_bart_state = Sampler.export_bart_state
     get_kept_trees = Sampler.get_kept_trees
     get_kept_trees_indexed = Sampler.get_kept_trees_indexed

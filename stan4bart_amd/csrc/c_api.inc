@@ -68,6 +68,9 @@ int S4B_FN(predict_bart)(s4b_sampler* s, const double* x_test, int64_t n_test, d
 int S4B_FN(predict_summary)(s4b_sampler* s, const s4b_summary_in* in, s4b_summary_out* out) {
   S4B_NEED(s, "predict_summary") S4B_TRY s->core.dev().bind(); s->core.predict_summary(in, out); S4B_CATCH
 }
+int S4B_FN(partial_dependence)(s4b_sampler* s, const s4b_pd_in* in, s4b_pd_out* out) {
+  S4B_NEED(s, "partial_dependence") S4B_TRY s->core.dev().bind(); s->core.partial_dependence(in, out); S4B_CATCH
+}
 int S4B_FN(export_bart_state)(s4b_sampler* s, void* buf, int64_t cap, int64_t* size) {
   S4B_NEED(s, "exportBARTState") S4B_TRY s->core.dev().bind(); if (!size) throw std::invalid_argument("exportBARTState: NULL size pointer"); *size = s->core.export_state(buf, cap); S4B_CATCH
 }

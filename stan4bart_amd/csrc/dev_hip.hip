@@ -1626,6 +1626,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 }
 
 #include "dev_summary.inc"
+#include "dev_pd.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
 static void use_device(int device) {
@@ -2729,6 +2730,8 @@ class DevHip {
 
   // s4b_predict_summary (dev_summary.inc): the same stream, everything uploaded for the call freed by it
   void predict_summary(const SummaryCall& c) { summary_run(stream_, a_.P, c, launches_); }
+  // s4b_partial_dependence (dev_pd.inc), likewise
+  void partial_dependence(const PdCall& c) { pd_run(stream_, a_.P, c, launches_); }
 
   // ---- Stan inputs
   void stan_inputs(int mode, bool wantTrain, double* cX, double* cZ, double* s0, double* trainOut) {

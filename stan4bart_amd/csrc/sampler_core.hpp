@@ -71,6 +71,20 @@ struct SummaryCall {
   double* mean; double* m2; double* average; int64_t* info;
 };
 
+// does the device layer form the partial dependence of the kept trees (s4b_partial_dependence)?  As has_predict_summary: refused where it is missing.
+template <class D, class = void> struct has_partial_dependence : std::false_type {};
+template <class D> struct has_partial_dependence<D, std::void_t<decltype(&D::partial_dependence)>> : std::true_type {};
+// one s4b_partial_dependence call as the device layer sees it: the rows as a SummaryCall (weights: one vector or NULL = 1 / rows; mean, m2, average
+// unused), the varied predictors, the grid binned as rows are, and per draw the tree order: the trees without a rule on a varied predictor in ascending
+// index (numBase[k] of them), then the others in ascending index
+struct PdCall {
+  SummaryCall rows;
+  int V, vars[2], G; const uint16_t* gridBin;          // [V x G]
+  const int32_t* order; const int32_t* numBase;        // [S x T], [S]
+  int64_t maxAffected, totalAffected;                  // trees with a rule on a varied predictor: the most in one draw, the sum over the draws
+  double* pd;                                          // [S x G]
+};
+
 template <class Dev>
 class SamplerCore {
  public:
@@ -524,38 +538,75 @@ class SamplerCore {
     if (!in || (!out->mean && !out->m2 && !out->average)) return S;          // query
     if constexpr (has_predict_summary<Dev>::value) {
       const int64_t nT = in->n_test;
-      if (nT < 1 || !in->x_test) throw std::invalid_argument("predict_summary: x_test must have at least one row");
-      if (in->n_weights < 0 || in->n_weights > 8) throw std::invalid_argument("predict_summary: between 0 and 8 weight vectors, not " + std::to_string(in->n_weights));
-      if (in->link != 0 && in->link != 1) throw std::invalid_argument("predict_summary: link must be 0 (identity) or 1 (standard normal cdf)");
-      if (in->n_dense < 0 || in->n_ell < 0) throw std::invalid_argument("predict_summary: negative n_dense or n_ell");
-      if (in->n_dense > 0 && (!in->dense || !in->dense_coef)) throw std::invalid_argument("predict_summary: n_dense > 0 needs dense and dense_coef");
-      if (in->n_ell > 0 && (!in->ell_index || !in->ell_value || !in->ell_coef || in->n_ell_coef < 1))
-        throw std::invalid_argument("predict_summary: n_ell > 0 needs ell_index, ell_value, ell_coef and n_ell_coef >= 1");
-      if (in->n_weights > 0 && !in->weights) throw std::invalid_argument("predict_summary: n_weights > 0 needs weights");
-      if (in->route < 0 || in->route > 2) throw std::invalid_argument("predict_summary: route must be 0 (automatic), 1 (staged) or 2 (global)");
-      if (in->stage_nodes < 0 || in->max_workgroups < 0) throw std::invalid_argument("predict_summary: negative stage_nodes or max_workgroups");
+      check_summary_rows(in, "predict_summary", 8);
       if (!out->mean || !out->m2 || (in->n_weights > 0 && !out->average)) throw std::invalid_argument("predict_summary: mean, m2 and (with weights) average must all be given");
-      for (size_t x = 0, m = (size_t)nT * (size_t)in->n_ell; x < m; ++x)
-        if (in->ell_index[x] < -1 || in->ell_index[x] >= in->n_ell_coef)
-          throw std::invalid_argument("predict_summary: ell_index " + std::to_string(in->ell_index[x]) + " outside [-1, " + std::to_string(in->n_ell_coef) + ")");
       if (S == 0) throw std::invalid_argument("predict_summary: the sampler holds no kept draws (bart_control.keep_trees, sampling runs)");
       std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
       bin_matrix(in->x_test, (size_t)nT, xb);
-      int64_t largest = 0;
-      for (int64_t k = 0; k < S; ++k) {
-        const int64_t en = k + 1 < S ? keptTreeStart_[(size_t)((k + 1) * T_)] : (int64_t)keptNodes_.size();
-        largest = std::max(largest, en - keptTreeStart_[(size_t)(k * T_)]);
-      }
-      SummaryCall c{};
-      c.xb = xb.data(); c.nT = nT; c.nodes = keptNodes_.data(); c.numNodes = keptNodes_.size(); c.treeStart = keptTreeStart_.data(); c.S = S; c.T = T_;
-      c.scale = keptScale_.data(); c.binary = binary_ ? 1 : 0; c.maxDrawNodes = largest;
-      c.offset = in->offset; c.M = in->n_dense; c.dense = in->dense; c.denseCoef = in->dense_coef;
-      c.E = in->n_ell; c.q = in->n_ell_coef; c.ellIndex = in->ell_index; c.ellValue = in->ell_value; c.ellCoef = in->ell_coef;
-      c.link = in->link; c.G = in->n_weights; c.weights = in->weights; c.route = in->route; c.stageNodes = in->stage_nodes; c.maxWorkgroups = in->max_workgroups;
+      SummaryCall c = summary_call(in, xb, S);
       c.mean = out->mean; c.m2 = out->m2; c.average = out->average; c.info = out->info;
       dev_.predict_summary(c);
       return S;
     } else throw std::invalid_argument("predict_summary: this device layer has no summary kernel (the summaries are formed by the HIP library only)");
+  }
+  // per draw the tree order of a partial-dependence call: the trees without a rule on vars[0 .. V) in ascending index, then the others in ascending
+  // index; numBase[k] = size of the first group.  One pass over keptNodes_ (slots that a tree has given up carry NODE_FREE: no rule).
+  void pd_tree_order(int V, const int32_t* vars, std::vector<int32_t>& order, std::vector<int32_t>& numBase, int64_t& maxAffected, int64_t& totalAffected) const {
+    const int64_t S = (int64_t)keptScale_.size() / 2;
+    order.resize((size_t)(S * T_)); numBase.resize((size_t)S); maxAffected = totalAffected = 0;
+    std::vector<int32_t> affected;
+    for (int64_t k = 0; k < S; ++k) {
+      affected.clear();
+      int32_t* o = order.data() + (size_t)(k * T_); int32_t nb = 0;
+      for (int t = 0; t < T_; ++t) {
+        const size_t x = (size_t)(k * T_ + t);
+        const int64_t en = x + 1 < keptTreeStart_.size() ? keptTreeStart_[x + 1] : (int64_t)keptNodes_.size();
+        bool hit = false;
+        for (int64_t u = keptTreeStart_[x]; u < en && !hit; ++u) { const int16_t v = keptNodes_[(size_t)u].var; hit = v >= 0 && (v == vars[0] || (V > 1 && v == vars[1])); }
+        if (hit) affected.push_back(t); else o[nb++] = t;
+      }
+      std::copy(affected.begin(), affected.end(), o + nb);
+      numBase[(size_t)k] = nb;
+      maxAffected = std::max<int64_t>(maxAffected, (int64_t)affected.size()); totalAffected += (int64_t)affected.size();
+    }
+  }
+  // s4b_partial_dependence: per kept draw and grid point the weighted row sum of the prediction with the predictors `vars` set to the grid point's
+  // values (the linear parts at the rows' own values), in one fused device call.  Everything is validated here, before any launch.  Live and stored samplers.
+  int64_t partial_dependence(const s4b_pd_in* in, s4b_pd_out* out) {
+    if (!out) throw std::invalid_argument("partial_dependence: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t S = (int64_t)keptScale_.size() / 2;
+    out->num_samples = S;
+    if (!in || !out->pd) return S;          // query
+    if constexpr (has_partial_dependence<Dev>::value) {
+      const std::string who = "partial_dependence";
+      check_summary_rows(&in->rows, who, 1);
+      if (in->n_vars != 1 && in->n_vars != 2) throw std::invalid_argument(who + ": one or two varied predictors, not " + std::to_string(in->n_vars));
+      for (int w = 0; w < in->n_vars; ++w)
+        if (in->vars[w] < 0 || in->vars[w] >= P_) throw std::invalid_argument(who + ": predictor " + std::to_string(in->vars[w]) + " outside [0, " + std::to_string(P_) + ")");
+      if (in->n_vars == 2 && in->vars[0] == in->vars[1]) throw std::invalid_argument(who + ": the two varied predictors must differ");
+      if (in->n_grid < 1 || in->n_grid > 64) throw std::invalid_argument(who + ": between 1 and 64 grid points per call, not " + std::to_string(in->n_grid));
+      if (!in->grid) throw std::invalid_argument(who + ": NULL grid");
+      const int V = in->n_vars, G = in->n_grid;
+      for (int x = 0; x < V * G; ++x) if (std::isnan(in->grid[x])) throw std::invalid_argument(who + ": the grid holds a NaN");
+      if (S == 0) throw std::invalid_argument(who + ": the sampler holds no kept draws (bart_control.keep_trees, sampling runs)");
+      const int64_t nT = in->rows.n_test;
+      std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
+      bin_matrix(in->rows.x_test, (size_t)nT, xb);
+      std::vector<uint16_t> gridBin((size_t)(V * G));          // bin_matrix's rule: the number of cuts strictly below the value
+      for (int w = 0; w < V; ++w) {
+        const std::vector<double>& c = cuts_[(size_t)in->vars[w]];
+        for (int g = 0; g < G; ++g) gridBin[(size_t)(w * G + g)] = (uint16_t)(std::lower_bound(c.begin(), c.end(), in->grid[w * G + g]) - c.begin());
+      }
+      PdCall c{};
+      c.rows = summary_call(&in->rows, xb, S); c.rows.info = out->info;
+      c.V = V; c.vars[0] = in->vars[0]; c.vars[1] = V > 1 ? in->vars[1] : -1; c.G = G; c.gridBin = gridBin.data(); c.pd = out->pd;
+      std::vector<int32_t> order, numBase;
+      pd_tree_order(V, in->vars, order, numBase, c.maxAffected, c.totalAffected);
+      c.order = order.data(); c.numBase = numBase.data();
+      dev_.partial_dependence(c);
+      return S;
+    } else throw std::invalid_argument("partial_dependence: this device layer has no partial-dependence kernel (it is formed by the HIP library only)");
   }
   // ---- sampler state as a byte string (layout: include/stan4bart_amd.h, s4b_get_state)
   int64_t get_state(void* buf, int64_t cap) {
@@ -908,6 +959,39 @@ class SamplerCore {
       cuts_[(size_t)j].resize((size_t)m);
       for (int c = 0; c < m; ++c) cuts_[(size_t)j][(size_t)c] = mn + (double)(c + 1) * (mx - mn) / (double)(m + 1);
     }
+  }
+  // what s4b_predict_summary and s4b_partial_dependence check of their rows (s4b_summary_in) before anything is launched
+  void check_summary_rows(const s4b_summary_in* in, const std::string& who, int maxWeights) const {
+    const int64_t nT = in->n_test;
+    if (nT < 1 || !in->x_test) throw std::invalid_argument(who + ": x_test must have at least one row");
+    if (in->n_weights < 0 || in->n_weights > maxWeights) throw std::invalid_argument(who + ": between 0 and " + std::to_string(maxWeights) + " weight vectors, not " + std::to_string(in->n_weights));
+    if (in->link != 0 && in->link != 1) throw std::invalid_argument(who + ": link must be 0 (identity) or 1 (standard normal cdf)");
+    if (in->n_dense < 0 || in->n_ell < 0) throw std::invalid_argument(who + ": negative n_dense or n_ell");
+    if (in->n_dense > 0 && (!in->dense || !in->dense_coef)) throw std::invalid_argument(who + ": n_dense > 0 needs dense and dense_coef");
+    if (in->n_ell > 0 && (!in->ell_index || !in->ell_value || !in->ell_coef || in->n_ell_coef < 1))
+      throw std::invalid_argument(who + ": n_ell > 0 needs ell_index, ell_value, ell_coef and n_ell_coef >= 1");
+    if (in->n_weights > 0 && !in->weights) throw std::invalid_argument(who + ": n_weights > 0 needs weights");
+    if (in->route < 0 || in->route > 2) throw std::invalid_argument(who + ": route must be 0 (automatic), 1 (staged) or 2 (global)");
+    if (in->stage_nodes < 0 || in->max_workgroups < 0) throw std::invalid_argument(who + ": negative stage_nodes or max_workgroups");
+    for (size_t x = 0, m = (size_t)nT * (size_t)in->n_ell; x < m; ++x)
+      if (in->ell_index[x] < -1 || in->ell_index[x] >= in->n_ell_coef)
+        throw std::invalid_argument(who + ": ell_index " + std::to_string(in->ell_index[x]) + " outside [-1, " + std::to_string(in->n_ell_coef) + ")");
+  }
+  // the rows of such a call as the device layer takes them: the kept trees, the largest draw, the validated arguments
+  SummaryCall summary_call(const s4b_summary_in* in, const std::vector<uint16_t>& xb, int64_t S) const {
+    const int64_t nT = in->n_test;
+    int64_t largest = 0;
+    for (int64_t k = 0; k < S; ++k) {
+      const int64_t en = k + 1 < S ? keptTreeStart_[(size_t)((k + 1) * T_)] : (int64_t)keptNodes_.size();
+      largest = std::max(largest, en - keptTreeStart_[(size_t)(k * T_)]);
+    }
+    SummaryCall c{};
+    c.xb = xb.data(); c.nT = nT; c.nodes = keptNodes_.data(); c.numNodes = keptNodes_.size(); c.treeStart = keptTreeStart_.data(); c.S = S; c.T = T_;
+    c.scale = keptScale_.data(); c.binary = binary_ ? 1 : 0; c.maxDrawNodes = largest;
+    c.offset = in->offset; c.M = in->n_dense; c.dense = in->dense; c.denseCoef = in->dense_coef;
+    c.E = in->n_ell; c.q = in->n_ell_coef; c.ellIndex = in->ell_index; c.ellValue = in->ell_value; c.ellCoef = in->ell_coef;
+    c.link = in->link; c.G = in->n_weights; c.weights = in->weights; c.route = in->route; c.stageNodes = in->stage_nodes; c.maxWorkgroups = in->max_workgroups;
+    return c;
   }
   void bin_matrix(const double* x, size_t m, std::vector<uint16_t>& out) const {
     auto work = [&](int j0, int j1) {

@@ -16,8 +16,11 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
+from .abi import PD_GRID_MAX
 from .fit import GroupTerm, chain_seeds, hip_sampler_factory, make_sampler_args, make_z_csr, qr_back_transform
 from .rcompat import RRng
+
+PD_LEVQUANTS = (0.05, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9, 0.95)          # dbarts pdbart's default levquants
 
 INT_MAX = 2147483647
 EXTRACT_TYPES = ("ev", "ppd", "fixef", "indiv.fixef", "ranef", "indiv.ranef", "indiv.bart", "sigma", "Sigma", "k", "varcount",
@@ -376,6 +379,23 @@ class Stan4bartFit:
             n = tot
         return n, mean, m2
 
+    def _summary_linear(self, type, X, groups, offset, sample_new_levels, rng):
+        """The linear parts and the link of a ``predict_summary`` / ``partial_dependence`` call: a function chain -> keyword arguments of the
+        sampler's method (fixed part ``dense = X - X_means`` with ``beta``, random part as ``_ell_random``'s table, the offset; "indiv.bart": none)."""
+        ev = type == "ev"
+        n_fixef, n_terms, n_chain = len(self._rows("beta.")), len(self.terms), len(self.samplers)
+        dense = dense_coef = ell_index = ell_value = ell_coef = None
+        if ev and X is not None and n_fixef:
+            beta = self.stan[self._rows("beta.")]                    # [K, iter, chain]
+            dense = np.asarray(X, dtype=np.float64).reshape(-1, n_fixef) - self.X_means
+            dense_coef = [np.ascontiguousarray(beta[:, :, c].T) for c in range(n_chain)]
+        if ev and groups is not None and len(groups) and n_terms:
+            order = {g.name: g for g in groups}
+            ell_index, ell_value, ell_coef = self._ell_random([order[g.name] for g in self.terms if g.name in order], sample_new_levels, rng)
+        link = 1 if (ev and self.family == "binomial") else 0
+        return lambda c: dict(offset=offset if ev else None, dense=dense, dense_coef=None if dense is None else dense_coef[c], ell_index=ell_index,
+                              ell_value=ell_value, ell_coef=None if ell_index is None else ell_coef[c], link=link)
+
     def predict_summary(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, type: str = "ev", row_weights=None,
                         combine_chains: bool = True, sample_new_levels: bool = True, seed: Optional[int] = None):
         """What users take from ``predict``'s [rows x draws] matrix, formed on the device without it (``s4b_predict_summary``, one call per chain):
@@ -400,28 +420,75 @@ class Stan4bartFit:
                 raise ValueError(f"row_weights must have shape [G, {rows}], not {w.shape}")
             if not 1 <= w.shape[0] <= 8:
                 raise ValueError(f"row_weights holds {w.shape[0]} weight vectors: between 1 and 8 per call")
-        rng = np.random.default_rng(seed)
-        ev = type == "ev"
-        n_fixef, n_terms, n_chain = len(self._rows("beta.")), len(self.terms), len(self.samplers)
-        dense = dense_coef = ell_index = ell_value = ell_coef = None
-        if ev and X is not None and n_fixef:
-            beta = self.stan[self._rows("beta.")]                    # [K, iter, chain]
-            dense = np.asarray(X, dtype=np.float64).reshape(-1, n_fixef) - self.X_means
-            dense_coef = [np.ascontiguousarray(beta[:, :, c].T) for c in range(n_chain)]
-        if ev and groups is not None and len(groups) and n_terms:
-            order = {g.name: g for g in groups}
-            ell_index, ell_value, ell_coef = self._ell_random([order[g.name] for g in self.terms if g.name in order], sample_new_levels, rng)
+        linear = self._summary_linear(type, X, groups, offset, sample_new_levels, np.random.default_rng(seed))
         parts, avgs = [], []
         for c, smp in enumerate(self.samplers):
-            r = smp.predict_summary(x_bart, offset=offset if ev else None, dense=dense, dense_coef=None if dense is None else dense_coef[c],
-                                    ell_index=ell_index, ell_value=ell_value, ell_coef=None if ell_index is None else ell_coef[c],
-                                    link=1 if (ev and self.family == "binomial") else 0, weights=w)
+            r = smp.predict_summary(x_bart, weights=w, **linear(c))
             parts.append((r["draws"], r["mean"], r["m2"]))
             avgs.append(r["average"].T)                              # [G, iter]
         n, mean, m2 = self._pool_chains(parts)
         sd = np.sqrt(m2 / (n - 1)) if n > 1 else np.full(rows, np.nan)
         average = np.stack(avgs, axis=2)
         return {"mean": mean, "sd": sd, "draws": int(n), "average": combine_chains_f(average) if combine_chains else average}
+
+    # ------------------------------------------------------------------ partial_dependence
+    @staticmethod
+    def pd_default_grid(column):
+        """dbarts' ``levquants`` of a column: its 0.05, 0.1, 0.2 ... 0.9, 0.95 quantiles (numpy's default interpolation, R's type 7)."""
+        return np.quantile(np.asarray(column, dtype=np.float64), PD_LEVQUANTS)
+
+    def partial_dependence(self, var, x_bart=None, grid=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, type: str = "ev",
+                           row_weights=None, probs=(0.025, 0.975), combine_chains: bool = True, sample_new_levels: bool = True,
+                           seed: Optional[int] = None):
+        """The partial dependence function of one BART predictor (``var`` an index into ``x_bart``'s columns) or of two jointly (a pair of indices):
+        per draw, the (weighted) average over the rows of the prediction with the predictor(s) set to each grid value — dbarts' ``pdbart`` /
+        ``pd2bart`` — in one fused device call per chain and 64 grid points (``s4b_partial_dependence``) instead of one ``predict`` per grid value.
+        ``grid`` None: the ``levquants`` quantiles of the column(s) of ``x_bart`` (a pair: their product, first predictor slowest); one predictor:
+        [G] values; a pair: [G x 2] points, or a tuple of two vectors whose product is taken.  The fixed and random parts are ``predict_summary``'s and
+        stay at the rows' own values.  ``row_weights`` None (the sample average) or [rows].  Returns ``grid``, ``pd`` [G, draws] ([G, iter, chain]
+        with ``combine_chains=False``) and ``mean``, ``lower``, ``upper`` [G]: mean and the ``probs`` quantiles over all draws and chains."""
+        if type == "ppd":
+            raise ValueError("partial_dependence does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("partial_dependence requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("partial_dependence needs x_bart, the rows of the BART predictors to average over")
+        x_bart = np.asarray(x_bart, dtype=np.float64)
+        rows, P = x_bart.shape
+        vs = [int(v) for v in np.atleast_1d(var)]
+        if len(vs) not in (1, 2) or len(set(vs)) != len(vs) or not all(0 <= v < P for v in vs):
+            raise ValueError(f"'var' must be one column index of x_bart or two different ones in [0, {P}), not {var!r}")
+        if grid is None:
+            grid = tuple(self.pd_default_grid(x_bart[:, v]) for v in vs)
+            grid = grid[0] if len(vs) == 1 else grid
+        if isinstance(grid, tuple):
+            if len(grid) != 2 or len(vs) != 2:
+                raise ValueError("a tuple of grid vectors is the product grid of a pair of predictors")
+            a, b = (np.asarray(t, dtype=np.float64).ravel() for t in grid)
+            grid = np.column_stack([np.repeat(a, len(b)), np.tile(b, len(a))])
+        grid = np.asarray(grid, dtype=np.float64)
+        pts = grid.reshape(-1, 1) if grid.ndim == 1 else grid
+        if pts.ndim != 2 or pts.shape[1] != len(vs) or not len(pts):
+            raise ValueError(f"grid must hold at least one point of {len(vs)} value(s), not shape {grid.shape}")
+        if np.isnan(pts).any():
+            raise ValueError("grid holds a NaN")
+        w = None
+        if row_weights is not None:
+            w = np.asarray(row_weights, dtype=np.float64)
+            if w.shape != (rows,):
+                raise ValueError(f"row_weights must have shape [{rows}], not {w.shape}")
+        linear = self._summary_linear(type, X, groups, offset, sample_new_levels, np.random.default_rng(seed))
+        per_chain = []
+        for c, smp in enumerate(self.samplers):
+            args = linear(c)
+            pieces = [smp.partial_dependence(x_bart, vs, pts[g0:g0 + PD_GRID_MAX], weights=w, **args)["pd"] for g0 in range(0, len(pts), PD_GRID_MAX)]
+            per_chain.append(np.concatenate(pieces, axis=1).T)                   # [G, iter]
+        pd = np.stack(per_chain, axis=2)
+        flat = combine_chains_f(pd)
+        lower, upper = np.quantile(flat, probs, axis=1)
+        return {"grid": grid, "pd": flat if combine_chains else pd, "mean": flat.mean(axis=1), "lower": lower, "upper": upper}
 
     def export_bart_states(self) -> list:
         """``stan4bart_exportBARTState`` per chain (reference R/stan4bart_fit.R:572-580): byte strings that
