@@ -306,6 +306,38 @@ typedef struct {
 } s4b_pd_out;
 int S4B_FN(partial_dependence)(s4b_sampler* s, const s4b_pd_in* in, s4b_pd_out* out);
 
+/* extension (R: apply(extract(fit), 1, quantile, probs), formed on the device): per-row QUANTILES of predict_summary's value v(i,k) — the same z, the
+ * same order of the additions, link 0 or 1 — over the kept draws of `s` AND of n_peers further samplers, pooled in one call: quantiles do not merge
+ * the way moments do, so the chains of a fit are handed to one call instead of one call each.  The pooled draws are those of `s`, then the peers' in
+ * their order, S in all (S <= 16384); a handle may occur more than once.  R's type 7 (numpy's default) over the sorted values x(0) <= ... <= x(S-1)
+ * of row i:     h = p (S - 1),  lo = floor(h),  hi = min(lo + 1, S - 1),  g = h - lo,  q = x(lo) + g (x(hi) - x(lo))     (g = 0: x(lo) unchanged)
+ * `rows` is predict_summary's input with n_weights 0; its dense_coef / ell_coef are the tables of `s` (one row per draw of `s`), peer_dense_coef[x] /
+ * peer_ell_coef[x] those of peer x (one row per draw of that peer).  The rows are binned once, with the cut points of `s`: every peer must have the
+ * same number of predictors and of trees per draw, the same kind of response and bit-identical cut points (samplers of one fit do), and must hold kept
+ * draws.  Everything is checked before anything is launched; a refused call leaves info all zero.  The rows are processed in chunks of C rows whose
+ * values (C x S doubles) are the only rows-times-draws storage of the call: C = scratch / (8 S) rounded down to a multiple of 64, at least 64, at most
+ * n_test, with scratch = scratch_bytes or the library's own limit.  Two calls, both routes, live and stored samplers, any order of
+ * the peers return the same bits.  out->quantiles = NULL (or in = NULL): only num_samples is set, to the kept draws of `s` alone. */
+typedef struct {
+  s4b_summary_in rows;
+  int32_t n_probs;                /* 1 .. 16 */
+  const double* probs;            /* each in [0, 1], no NaN; duplicates and any order allowed */
+  int32_t n_peers;                /* >= 0 */
+  s4b_sampler* const* peers;      /* live (kept trees) or stored samplers */
+  const double* const* peer_dense_coef;   /* [n_peers] tables (peer's draws x n_dense), NULL when n_dense = 0 */
+  const double* const* peer_ell_coef;     /* [n_peers] tables (peer's draws x n_ell_coef), NULL when n_ell = 0 */
+  int64_t scratch_bytes;          /* 0, or an upper limit below the library's own on the value scratch (fewer rows per chunk) */
+} s4b_quantile_in;
+typedef struct {
+  double* quantiles;              /* n_probs x n_test, prob-major: quantiles[j * n_test + i] */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did: [0] route of the value kernel (1 LDS-staged, 2 global; 0: nothing was launched), [1] rows per chunk C, [2] chunks,
+   * [3] (rows sorted side by side per workgroup) << 32 | draws padded to a power of two, [4] nodes of the largest pooled draw, [5] kernel launches
+   * (2 per chunk), [6] bytes of device memory the call allocated, [7] pooled draws */
+  int64_t info[8];
+} s4b_quantile_out;
+int S4B_FN(predict_quantiles)(s4b_sampler* s, const s4b_quantile_in* in, s4b_quantile_out* out);
+
 /* The state of a chain BETWEEN TWO GIBBS ITERATIONS as one relocatable byte string: what the next iteration starts from.  It is
  * the hook of the teacher-forced parity tests (state of one implementation injected into the other before every compared
  * transition) and lets a chain continue in another sampler created from the same data; it is not an archive of a fit: the

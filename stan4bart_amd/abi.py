@@ -103,9 +103,19 @@ class PdOut(C.Structure):              # s4b_pd_out
     _fields_ = [("pd", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
 
 
+class QuantileIn(C.Structure):         # s4b_quantile_in
+    _fields_ = [("rows", SummaryIn), ("n_probs", C.c_int32), ("probs", c_double_p), ("n_peers", C.c_int32), ("peers", C.POINTER(C.c_void_p)),
+                ("peer_dense_coef", C.POINTER(c_double_p)), ("peer_ell_coef", C.POINTER(c_double_p)), ("scratch_bytes", C.c_int64)]
+
+
+class QuantileOut(C.Structure):        # s4b_quantile_out
+    _fields_ = [("quantiles", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
 SUMMARY_ROUTES = {"auto": 0, "staged": 1, "global": 2}
 SUMMARY_INFO = ("route", "rows_per_tile", "workgroups", "staging_bytes", "largest_draw_nodes", "launches", "device_bytes", "staging_nodes")
 PD_INFO = SUMMARY_INFO[:7] + ("largest_affected", "total_affected")          # (the last two share info[7]: trees with a rule on a varied predictor)
+QUANTILE_INFO = ("route", "rows_per_chunk", "chunks", "rows_per_sort", "padded_draws", "largest_draw_nodes", "launches", "device_bytes", "draws")
 PD_GRID_MAX = 64                       # grid points per s4b_partial_dependence call
 
 
@@ -331,6 +341,7 @@ class Sampler:
             "set_tree_path": [vp, i32], "get_tree_path": [vp, ip], "get_fused_stats": [vp, C.POINTER(i64)], "get_sweep_stats": [vp, C.POINTER(i64)], "get_sweep_busy": [vp, C.POINTER(i64)], "get_sweep_spec": [vp, C.POINTER(i64)], "set_test_hook": [vp, i32, i64], "set_hmc_mode": [vp, i32], "get_hmc_mode": [vp, ip],
             "predict_summary": [vp, C.POINTER(SummaryIn), C.POINTER(SummaryOut)],
             "partial_dependence": [vp, C.POINTER(PdIn), C.POINTER(PdOut)],
+            "predict_quantiles": [vp, C.POINTER(QuantileIn), C.POINTER(QuantileOut)],
             "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
         }
         for name, argtypes in sig.items():
@@ -734,6 +745,56 @@ class Sampler:
         del keep, buf
         return dict(pd=pd, draws=int(out.num_samples), info=dict(self.pd_info))
 
+    def predict_quantiles(self, x_test: np.ndarray, probs, peers=(), peer_dense_coef=None, peer_ell_coef=None, offset=None, dense=None, dense_coef=None,
+                          ell_index=None, ell_value=None, ell_coef=None, link: int = 0, route="auto", stage_nodes: int = 0, scratch_bytes: int = 0) -> dict:
+        """``s4b_predict_quantiles``: per row the ``probs`` quantiles (R's type 7, numpy's default) of ``predict_summary``'s value over the kept draws
+        of this sampler and of ``peers`` (samplers or stored samplers of the same model: the chains of a fit), pooled in ONE device call, without the
+        [rows x draws] matrix.  ``dense_coef`` / ``ell_coef`` are this sampler's tables, ``peer_dense_coef`` / ``peer_ell_coef`` lists of the
+        peers' ([peer's draws x M], [peer's draws x q]); the other arguments as ``predict_summary`` takes them.  ``scratch_bytes`` limits the values
+        held at once (fewer rows per chunk).  Returns dict(quantiles [Q x rows], draws: the pooled count, info: QUANTILE_INFO)."""
+        fn = getattr(self._lib, self._pfx + "predict_quantiles", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_quantiles")
+
+        def draws(smp):
+            probe = QuantileOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if pr.ndim != 1:
+            raise ValueError(f"probs must be a vector, not shape {pr.shape}")
+        peers = list(peers)
+        rows_in, keep, rows, _ = self._summary_in(draws(self), x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, None, route,
+                                                   stage_nodes, 0)
+
+        def tables(given, cols, what):          # one C-ordered [peer's draws x cols] table per peer, as an array of pointers
+            if not cols or not peers or given is None:          # (tables missing though needed: the library refuses the call)
+                return None, []
+            if len(given) != len(peers):
+                raise ValueError(f"{what} must hold one table per peer ({len(peers)})")
+            held = []
+            for x, (t, smp) in enumerate(zip(given, peers)):
+                t = np.asarray(t)
+                if t.shape != (draws(smp), cols):
+                    raise ValueError(f"{what}[{x}] must be [{draws(smp)} x {cols}], not shape {t.shape}")
+                held.append(_f64(t, "C"))
+            return (c_double_p * len(held))(*[_dp(t) for t in held]), held
+        pdc, hold_d = tables(peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
+        pec, hold_e = tables(peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
+        handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
+        q = np.zeros((len(pr), rows))
+        buf = q if q.size else np.zeros(1)          # (no prob: refused by the library, which needs a pointer to tell the call from a query)
+        arg = QuantileIn(rows=rows_in, n_probs=len(pr), probs=_dp(pr), n_peers=len(peers), peers=handles if peers else None, peer_dense_coef=pdc,
+                         peer_ell_coef=pec, scratch_bytes=int(scratch_bytes))
+        out = QuantileOut(quantiles=_dp(buf))
+        self.quantile_info = dict(zip(QUANTILE_INFO, [0] * 9))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        w = [int(v) for v in out.info]
+        self.quantile_info = dict(zip(QUANTILE_INFO, w[:3] + [w[3] >> 32, w[3] & 0xFFFFFFFF] + w[4:]))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep, hold_d, hold_e, buf
+        return dict(quantiles=q, draws=int(out.num_samples), info=dict(self.quantile_info))
+
     def profile_leapfrog(self, n_evals: int = 10) -> dict:
         """Per-leapfrog O(N) sums of the hmc_mode 1 path timed with HIP events (measurement hook of the HIP library)."""
         out = (C.c_double * 8)()
@@ -852,6 +913,7 @@ class StoredSampler:
     predict_summary = Sampler.predict_summary
     _summary_in = staticmethod(Sampler._summary_in)
     partial_dependence = Sampler.partial_dependence
+    predict_quantiles = Sampler.predict_quantiles
     export_bart_state = Sampler.export_bart_state
     get_kept_trees = Sampler.get_kept_trees
     get_kept_trees_indexed = Sampler.get_kept_trees_indexed

@@ -1627,6 +1627,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 
 #include "dev_summary.inc"
 #include "dev_pd.inc"
+#include "dev_quantile.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
 static void use_device(int device) {
@@ -2732,6 +2733,8 @@ class DevHip {
   void predict_summary(const SummaryCall& c) { summary_run(stream_, a_.P, c, launches_); }
   // s4b_partial_dependence (dev_pd.inc), likewise
   void partial_dependence(const PdCall& c) { pd_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_quantiles (dev_quantile.inc), likewise
+  void predict_quantiles(const QuantileCall& c) { quantile_run(stream_, a_.P, c, launches_); }
 
   // ---- Stan inputs
   void stan_inputs(int mode, bool wantTrain, double* cX, double* cZ, double* s0, double* trainOut) {

@@ -85,6 +85,18 @@ struct PdCall {
   double* pd;                                          // [S x G]
 };
 
+// does the device layer form per-row quantiles over the pooled kept draws of several samplers (s4b_predict_quantiles)?  As has_partial_dependence.
+template <class D, class = void> struct has_predict_quantiles : std::false_type {};
+template <class D> struct has_predict_quantiles<D, std::void_t<decltype(&D::predict_quantiles)>> : std::true_type {};
+// one s4b_predict_quantiles call as the device layer sees it: the rows as a SummaryCall over the POOLED draws (nodes, tree starts, scales and the
+// coefficient tables of the sampler and its peers concatenated, S and maxDrawNodes of the pool; weights, mean, m2, average unused)
+struct QuantileCall {
+  SummaryCall rows;
+  int Q; const double* probs;          // [Q], each in [0, 1]
+  int64_t scratchBytes;                // 0, or an upper limit on the value scratch of a chunk of rows
+  double* quantiles;                   // [Q x nT], prob-major
+};
+
 template <class Dev>
 class SamplerCore {
  public:
@@ -607,6 +619,87 @@ class SamplerCore {
       dev_.partial_dependence(c);
       return S;
     } else throw std::invalid_argument("partial_dependence: this device layer has no partial-dependence kernel (it is formed by the HIP library only)");
+  }
+  // s4b_predict_quantiles: per row the type-7 quantiles of predict_summary's value over the kept draws of this sampler and of `peers` (n_peers of
+  // them, in this order behind its own), in one device call that sees all of them.  The rows are binned once, with this sampler's cut points, so a
+  // peer must carry the same predictors, trees per draw, response kind and bit-identical cut points.  Everything is validated here, before any launch.
+  int64_t predict_quantiles(const s4b_quantile_in* in, s4b_quantile_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_quantiles: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in || !out->quantiles) return own;          // query
+    if constexpr (has_predict_quantiles<Dev>::value) {
+      const std::string who = "predict_quantiles";
+      const s4b_summary_in* rw = &in->rows;
+      check_summary_rows(rw, who, 8);
+      if (rw->n_weights != 0) throw std::invalid_argument(who + ": n_weights must be 0 (the quantiles are per row), not " + std::to_string(rw->n_weights));
+      if (in->n_probs < 1 || in->n_probs > 16) throw std::invalid_argument(who + ": between 1 and 16 probs per call, not " + std::to_string(in->n_probs));
+      if (!in->probs) throw std::invalid_argument(who + ": NULL probs");
+      for (int j = 0; j < in->n_probs; ++j)
+        if (!(in->probs[j] >= 0.0 && in->probs[j] <= 1.0)) throw std::invalid_argument(who + ": prob " + std::to_string(in->probs[j]) + " outside [0, 1]");
+      if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
+      const int np = in->n_peers;
+      if (np < 0) throw std::invalid_argument(who + ": negative n_peers");
+      if (np > 0 && (!in->peers || !peers)) throw std::invalid_argument(who + ": n_peers > 0 needs peers");
+      if (np > 0 && rw->n_dense > 0 && !in->peer_dense_coef) throw std::invalid_argument(who + ": n_dense > 0 needs peer_dense_coef, one table per peer");
+      if (np > 0 && rw->n_ell > 0 && !in->peer_ell_coef) throw std::invalid_argument(who + ": n_ell > 0 needs peer_ell_coef, one table per peer");
+      if (own == 0) throw std::invalid_argument(who + ": the sampler holds no kept draws (bart_control.keep_trees, sampling runs)");
+      int64_t S = own;
+      for (int x = 0; x < np; ++x) {
+        const SamplerCore* pc = peers[x];
+        const std::string pw = who + ": peer " + std::to_string(x);
+        if (!pc) throw std::invalid_argument(pw + " is a NULL sampler");
+        if (pc->P_ != P_) throw std::invalid_argument(pw + " has " + std::to_string(pc->P_) + " BART predictors, the sampler " + std::to_string(P_));
+        if (pc->T_ != T_) throw std::invalid_argument(pw + " has " + std::to_string(pc->T_) + " trees per draw, the sampler " + std::to_string(T_));
+        if (pc->binary_ != binary_) throw std::invalid_argument(pw + (pc->binary_ ? " has a binary response, the sampler a continuous one" : " has a continuous response, the sampler a binary one"));
+        for (int j = 0; j < P_; ++j) {
+          const std::vector<double>& ca = cuts_[(size_t)j]; const std::vector<double>& cb = pc->cuts_[(size_t)j];
+          if (ca.size() != cb.size() || (ca.size() && std::memcmp(ca.data(), cb.data(), ca.size() * 8) != 0))
+            throw std::invalid_argument(pw + " has other cut points of predictor " + std::to_string(j) + " than the sampler (the rows are binned once: pooled samplers must share their training predictors)");
+        }
+        const int64_t ps = (int64_t)pc->keptScale_.size() / 2;
+        if (ps == 0) throw std::invalid_argument(pw + " holds no kept draws (bart_control.keep_trees, sampling runs)");
+        if (rw->n_dense > 0 && !in->peer_dense_coef[x]) throw std::invalid_argument(pw + ": n_dense > 0 needs its dense_coef table");
+        if (rw->n_ell > 0 && !in->peer_ell_coef[x]) throw std::invalid_argument(pw + ": n_ell > 0 needs its ell_coef table");
+        S += ps;
+      }
+      if (S > 16384) throw std::invalid_argument(who + ": " + std::to_string(S) + " pooled draws, at most 16384 (one row of the sort as doubles in the LDS of a compute unit)");
+      const int64_t nT = rw->n_test;
+      std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
+      bin_matrix(rw->x_test, (size_t)nT, xb);
+      QuantileCall c{};
+      c.rows = summary_call(rw, xb, own); c.rows.info = out->info; c.rows.G = 0; c.rows.weights = nullptr;
+      c.Q = in->n_probs; c.probs = in->probs; c.scratchBytes = in->scratch_bytes; c.quantiles = out->quantiles;
+      // the pool: this sampler's draws, then the peers' in their order; tree starts rebased onto the concatenated nodes
+      std::vector<PackedNode> nodes; std::vector<int64_t> treeStart; std::vector<double> scale, denseCoef, ellCoef;
+      if (np > 0) {
+        const size_t M = (size_t)rw->n_dense, q = rw->n_ell > 0 ? (size_t)rw->n_ell_coef : 0;
+        size_t numNodes = keptNodes_.size();
+        for (int x = 0; x < np; ++x) numNodes += peers[x]->keptNodes_.size();
+        nodes.reserve(numNodes); treeStart.reserve((size_t)S * (size_t)T_); scale.reserve((size_t)S * 2);
+        denseCoef.reserve((size_t)S * M); ellCoef.reserve((size_t)S * q);
+        for (int x = -1; x < np; ++x) {
+          const SamplerCore* pc = x < 0 ? this : peers[x];
+          const size_t ps = pc->keptScale_.size() / 2;
+          const int64_t base = (int64_t)nodes.size();
+          for (int64_t st : pc->keptTreeStart_) treeStart.push_back(st + base);
+          nodes.insert(nodes.end(), pc->keptNodes_.begin(), pc->keptNodes_.end());
+          scale.insert(scale.end(), pc->keptScale_.begin(), pc->keptScale_.end());
+          const double* dc = x < 0 ? rw->dense_coef : in->peer_dense_coef ? in->peer_dense_coef[x] : nullptr;
+          const double* ec = x < 0 ? rw->ell_coef : in->peer_ell_coef ? in->peer_ell_coef[x] : nullptr;
+          if (M) denseCoef.insert(denseCoef.end(), dc, dc + ps * M);
+          if (q) ellCoef.insert(ellCoef.end(), ec, ec + ps * q);
+          c.rows.maxDrawNodes = std::max(c.rows.maxDrawNodes, pc->summary_call(rw, xb, (int64_t)ps).maxDrawNodes);
+        }
+        c.rows.nodes = nodes.data(); c.rows.numNodes = nodes.size(); c.rows.treeStart = treeStart.data(); c.rows.scale = scale.data(); c.rows.S = S;
+        if (M) c.rows.denseCoef = denseCoef.data();
+        if (q) c.rows.ellCoef = ellCoef.data();
+      }
+      dev_.predict_quantiles(c);
+      out->num_samples = S;
+      return S;
+    } else throw std::invalid_argument("predict_quantiles: this device layer has no quantile kernels (the quantiles are formed by the HIP library only)");
   }
   // ---- sampler state as a byte string (layout: include/stan4bart_amd.h, s4b_get_state)
   int64_t get_state(void* buf, int64_t cap) {

@@ -490,6 +490,33 @@ class Stan4bartFit:
         lower, upper = np.quantile(flat, probs, axis=1)
         return {"grid": grid, "pd": flat if combine_chains else pd, "mean": flat.mean(axis=1), "lower": lower, "upper": upper}
 
+    # ------------------------------------------------------------------ predict_quantiles
+    def predict_quantiles(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, type: str = "ev",
+                          probs=(0.025, 0.5, 0.975), sample_new_levels: bool = True, seed: Optional[int] = None):
+        """The per-row credible interval — ``apply(extract(fit), 1, quantile, probs)`` — formed on the device without ``predict``'s [rows x draws]
+        matrix: the ``probs`` quantiles (R's type 7) of the expected value of each row over all draws and chains, in ONE pooled call
+        (``s4b_predict_quantiles``: the first chain's sampler with the others as its peers; quantiles of chains cannot be merged afterwards).
+        ``type`` "ev" or "indiv.bart"; for a given ``seed`` the draws of unseen levels are ``predict``'s.  Needs bart_args keepTrees.
+        Returns ``probs``, ``quantiles`` [Q, rows] and ``draws``, the pooled count."""
+        if type == "ppd":
+            raise ValueError("predict_quantiles does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("predict_quantiles requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_quantiles needs x_bart, the new rows of the BART predictors")
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or not len(pr) or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of values in [0, 1], not {probs!r}")
+        x_bart = np.asarray(x_bart, dtype=np.float64)
+        linear = self._summary_linear(type, X, groups, offset, sample_new_levels, np.random.default_rng(seed))
+        first, others = linear(0), [linear(c) for c in range(1, len(self.samplers))]
+        r = self.samplers[0].predict_quantiles(x_bart, pr, peers=self.samplers[1:],
+                                               peer_dense_coef=None if first["dense"] is None else [a["dense_coef"] for a in others],
+                                               peer_ell_coef=None if first["ell_index"] is None else [a["ell_coef"] for a in others], **first)
+        return {"probs": pr, "quantiles": r["quantiles"], "draws": r["draws"]}
+
     def export_bart_states(self) -> list:
         """``stan4bart_exportBARTState`` per chain (reference R/stan4bart_fit.R:572-580): byte strings that
         ``attach_stored_samplers`` turns back into predict-capable samplers, in this or another process."""
