@@ -1,6 +1,5 @@
 // Per-row quantiles of the kept draws' predictions, pooled over several samplers (s4b_predict_quantiles; DESIGN.md 5.7).
-// Included by dev_hip.hip inside namespace s4b, after dev_pd.inc: WalkNode, walk_node, the tile / draw loop and the staging are k_predict_summary's,
-// pd_phi is dev_pd.inc's out-of-line Phi.
+// Included by dev_hip.hip inside namespace s4b, after dev_summary.inc and, through it, dev_readout.inc: the walk, the staging, the linear part, the out-of-line Phi and the route are there.
 //
 // The host hands down ONE pooled description (QuantileCall.rows: the kept draws of the sampler and its peers concatenated, S draws) and loops over
 // chunks of C rows.  Per chunk two launches on the sampler's stream:
@@ -27,18 +26,12 @@ constexpr int QT_PROBS_MAX = 16;
 #endif
 constexpr int64_t QT_SCRATCH_DEFAULT = (int64_t)S4B_QT_SCRATCH_MIB << 20;   // value scratch of a chunk at most
 
-struct QuantileDev {         // device pointers of one call
-  const uint16_t* xb; const PackedNode* nodes; const int64_t* treeStart; const double* scale;
-  const double* offset; const double* dense; const double* denseCoef; const int32_t* ellIndex; const double* ellValue; const double* ellCoef;
+struct QuantileDev : RowsDev {
   double* vals;              // [C x S], row-major
   const double* probs; double* quantiles;          // [Q], [Q x nT]
-  int64_t nT, S, numNodes, chunk0, chunkRows, segDraws;          // segDraws: draws per workgroup of k_predict_values, a multiple of QT_GROUP
-  int T, binary, M, E, q, link, stageNodes, Q, Sp, R;
+  int64_t chunk0, chunkRows, segDraws;          // segDraws: draws per workgroup of k_predict_values, a multiple of QT_GROUP
+  int Q, Sp, R;
 };
-
-static size_t quantile_lds_bytes(bool staged, int stageNodes, int T) {          // two staging buffers: the nodes and the tree starts
-  return staged ? (size_t)2 * ((size_t)stageNodes * sizeof(WalkNode) + (size_t)T * 4) : 0;
-}
 
 template <bool STAGED>
 __global__ __launch_bounds__(PS_BLOCK) void k_predict_values(QuantileDev a) {
@@ -46,73 +39,30 @@ __global__ __launch_bounds__(PS_BLOCK) void k_predict_values(QuantileDev a) {
   WalkNode* nbuf = (WalkNode*)qv_lds;                                              // [2][stageNodes]
   int32_t* sbuf = (int32_t*)(qv_lds + (size_t)2 * a.stageNodes * sizeof(WalkNode));   // [2][T]: tree starts inside the draw
   const int tid = threadIdx.x, T = a.T;
-  const int64_t nT = a.nT, S = a.S, C = a.chunkRows;
+  const int64_t S = a.S, C = a.chunkRows;
   const int64_t tiles = (C + PS_BLOCK - 1) / PS_BLOCK;
-  auto draw_first = [&](int64_t k) { return a.treeStart[k * T]; };
-  auto draw_count = [&](int64_t k) { return (int)min((int64_t)a.stageNodes, (k + 1 < S ? a.treeStart[(k + 1) * T] : a.numNodes) - a.treeStart[k * T]); };
 
   // the draws of this workgroup (blockIdx.y): the values of different draws share nothing, so a chunk with few tiles still fills the device
   const int64_t k0 = (int64_t)blockIdx.y * a.segDraws, k1 = min(S, k0 + a.segDraws);
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t r = tile * PS_BLOCK + tid;      // row inside the chunk
     const bool act = r < C;
-    const int64_t ii = a.chunk0 + (act ? r : C - 1);          // threads beyond the chunk's last row walk that row and store nothing
+    const size_t ii = (size_t)(a.chunk0 + (act ? r : C - 1));        // threads beyond the chunk's last row walk that row and store nothing
     const double off = a.offset ? a.offset[ii] : 0.0;
     double* out = a.vals + (size_t)(act ? r : 0) * (size_t)S;
     double grp[QT_GROUP];
 #pragma unroll
     for (int u = 0; u < QT_GROUP; ++u) grp[u] = 0.0;
     __syncthreads();                              // the tile before is done with the staging buffers
-    if (STAGED) {
-      const int64_t first = draw_first(k0); const int cnt = draw_count(k0);
-      for (int u = tid; u < cnt; u += PS_BLOCK) nbuf[u] = walk_node(a.nodes[first + u]);
-      for (int t = tid; t < T; t += PS_BLOCK) sbuf[t] = (int32_t)(a.treeStart[k0 * T + t] - first);
-      __syncthreads();
-    }
+    if (STAGED) { stage_draw<false>(a, k0, nbuf, sbuf, nullptr); __syncthreads(); }
     for (int64_t k = k0; k < k1; ++k) {
       const int b = (int)((k - k0) & 1);
-      if (STAGED && k + 1 < k1) {                  // draw k + 1 into the other buffer (last read in draw k - 1, before that draw's barrier)
-        const int64_t first = draw_first(k + 1); const int cnt = draw_count(k + 1);
-        WalkNode* dst = nbuf + (size_t)(b ^ 1) * a.stageNodes;
-        for (int u = tid; u < cnt; u += PS_BLOCK) dst[u] = walk_node(a.nodes[first + u]);
-        for (int t = tid; t < T; t += PS_BLOCK) sbuf[(size_t)(b ^ 1) * T + t] = (int32_t)(a.treeStart[(k + 1) * T + t] - first);
-      }
-      // ---- the walk: k_predict_summary's, four trees at a time, the leaf values added in tree order
-      const WalkNode* lbase = nbuf + (size_t)b * a.stageNodes;
-      const int32_t* lstart = sbuf + (size_t)b * T;
-      double f = 0.0;
-      for (int t0 = 0; t0 < T; t0 += PS_WALK) {
-        WalkNode p[PS_WALK];
-        const WalkNode* ls[PS_WALK]; const PackedNode* gs[PS_WALK];
-#pragma unroll
-        for (int u = 0; u < PS_WALK; ++u) {
-          const int t = min(t0 + u, T - 1);
-          if (STAGED) { ls[u] = lbase + lstart[t]; p[u] = ls[u][0]; }
-          else { gs[u] = a.nodes + a.treeStart[k * T + t]; p[u] = walk_node(gs[u][0]); }
-        }
-        bool more = true;
-        for (int guard = 0; more && guard < 32768; ++guard) {          // (the step cap: k_predict_summary's second guard)
-          more = false;
-#pragma unroll
-          for (int u = 0; u < PS_WALK; ++u) {
-            if (p[u].var >= 0) {
-              const int nd = (a.xb[(size_t)p[u].var * (size_t)nT + (size_t)ii] <= p[u].cut) ? p[u].left : p[u].right;
-              if (STAGED) p[u] = ls[u][nd]; else p[u] = walk_node(gs[u][nd]);
-              more |= p[u].var >= 0;
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < PS_WALK; ++u) if (t0 + u < T) f += p[u].mu;
-      }
-      double z = a.binary ? f : (f + 0.5) * a.scale[2 * k + 1] + a.scale[2 * k];
+      // draw k + 1 into the other buffer (last read in draw k - 1, before that draw's barrier)
+      if (STAGED && k + 1 < k1) stage_draw<false>(a, k + 1, nbuf + (size_t)(b ^ 1) * a.stageNodes, sbuf + (size_t)(b ^ 1) * T, nullptr);
+      double z = response_scale(a, k, walk_all<STAGED>(a, nbuf + (size_t)b * a.stageNodes, sbuf + (size_t)b * T, k, ii));
       if (a.offset) z += off;
-      for (int j = 0; j < a.M; ++j) z += a.dense[(size_t)j * (size_t)nT + (size_t)ii] * a.denseCoef[k * a.M + j];
-      for (int e = 0; e < a.E; ++e) {
-        const int32_t c = a.ellIndex[(size_t)e * (size_t)nT + (size_t)ii];
-        if (c >= 0) z += a.ellValue[(size_t)e * (size_t)nT + (size_t)ii] * a.ellCoef[k * a.q + c];
-      }
-      const double v = a.link ? pd_phi(z) : z;
+      z = add_linear(z, a, k, ii);
+      const double v = a.link ? readout_phi(z) : z;
       // ---- draw k into its place of the group (selects, not an indexed array: the group stays in registers); a full group leaves at once
       const int slot = (int)(k % QT_GROUP);
 #pragma unroll
@@ -172,75 +122,43 @@ __global__ __launch_bounds__(QT_BLOCK) void k_row_quantiles(QuantileDev a) {
   }
 }
 
-// the route of the value kernel: summary_plan's rule with this kernel's LDS (no reduction space)
-static SummaryPlan quantile_plan(const SummaryCall& r) {
-  SummaryPlan p;
-  p.stageNodes = r.stageNodes > 0 ? std::min(r.stageNodes, PS_STAGE_NODES) : (int)std::min<int64_t>(PS_STAGE_NODES, (r.maxDrawNodes + 63) / 64 * 64);
-  const bool fits = r.maxDrawNodes <= p.stageNodes && quantile_lds_bytes(true, p.stageNodes, r.T) <= PS_LDS_MAX;
-  p.staged = r.route != 2 && fits;
-  if (!p.staged) p.stageNodes = 0;
-  p.lds = quantile_lds_bytes(p.staged, p.stageNodes, r.T);
-  p.workgroups = 0;          // per chunk
-  return p;
-}
-
 // uploads, two launches per chunk of rows, the download — on `stream`, everything allocated here freed here (summary_run's discipline)
 static void quantile_run(hipStream_t stream, int P, const QuantileCall& c, int64_t& launches) {
   const SummaryCall& r = c.rows;
-  const SummaryPlan plan = quantile_plan(r);
-  std::vector<void*> held; int64_t bytes = 0;
-  auto freeAll = [&] { for (void* q : held) (void)hipFree(q); held.clear(); };
-  auto dev = [&](const void* src, size_t n) -> void* {          // a device copy of n host bytes (src NULL: uninitialised)
-    void* q = nullptr; const size_t need = std::max<size_t>(16, n);
-    HIP_OK(hipMalloc(&q, need)); held.push_back(q); bytes += (int64_t)need;
-    if (src && n) HIP_OK(hipMemcpyAsync(q, src, n, hipMemcpyHostToDevice, stream));
-    return q;
-  };
-  try {
-    const size_t nT = (size_t)r.nT, S = (size_t)r.S, Q = (size_t)c.Q;
-    // rows per chunk: what the scratch holds, a multiple of 64, at least 64, at most all rows
-    const int64_t scratch = c.scratchBytes > 0 ? std::min(c.scratchBytes, QT_SCRATCH_DEFAULT) : QT_SCRATCH_DEFAULT;
-    const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(64, scratch / (8 * r.S) / 64 * 64));
-    const int64_t chunks = (r.nT + C - 1) / C;
-    int Sp = 1; while (Sp < r.S) Sp <<= 1;
-    const int R = std::max(1, QT_SORT / Sp);
-    const size_t sortLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT);
-    QuantileDev a{};
-    a.xb = (const uint16_t*)dev(r.xb, (size_t)P * nT * 2);
-    a.nodes = (const PackedNode*)dev(r.nodes, r.numNodes * sizeof(PackedNode));
-    a.treeStart = (const int64_t*)dev(r.treeStart, S * (size_t)r.T * 8);
-    a.scale = (const double*)dev(r.scale, S * 16);
-    a.offset = r.offset ? (const double*)dev(r.offset, nT * 8) : nullptr;
-    if (r.M) { a.dense = (const double*)dev(r.dense, nT * (size_t)r.M * 8); a.denseCoef = (const double*)dev(r.denseCoef, S * (size_t)r.M * 8); }
-    if (r.E) {
-      a.ellIndex = (const int32_t*)dev(r.ellIndex, nT * (size_t)r.E * 4); a.ellValue = (const double*)dev(r.ellValue, nT * (size_t)r.E * 8);
-      a.ellCoef = (const double*)dev(r.ellCoef, S * (size_t)r.q * 8);
-    }
-    a.vals = (double*)dev(nullptr, (size_t)C * S * 8);
-    a.probs = (const double*)dev(c.probs, Q * 8);
-    a.quantiles = (double*)dev(nullptr, Q * nT * 8);
-    a.nT = r.nT; a.S = r.S; a.numNodes = (int64_t)r.numNodes; a.T = r.T; a.binary = r.binary; a.M = r.M; a.E = r.E; a.q = r.q; a.link = r.link;
-    a.stageNodes = plan.stageNodes; a.Q = c.Q; a.Sp = Sp; a.R = R;
-    if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_predict_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-    HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortLds));
-    for (int64_t ch = 0; ch < chunks; ++ch) {
-      a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0);
-      const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
-      // segments of draws: enough to reach QT_FILL workgroups, each of at least QT_SEG_MIN draws and a multiple of QT_GROUP (a thread's store groups stay whole)
-      const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
-      a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
-      const int segs = (int)((r.S + a.segDraws - 1) / a.segDraws);
-      if (plan.staged) hipLaunchKernelGGL(k_predict_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, a);
-      else hipLaunchKernelGGL(k_predict_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, a);
-      HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
-      const int sg = (int)((a.chunkRows + R - 1) / R);
-      hipLaunchKernelGGL(k_row_quantiles, dim3(sg), dim3(QT_BLOCK), sortLds, stream, a);
-      HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
-    }
-    HIP_OK(hipMemcpyAsync(c.quantiles, a.quantiles, Q * nT * 8, hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    r.info[0] = plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = ((int64_t)R << 32) | (int64_t)Sp;
-    r.info[4] = r.maxDrawNodes; r.info[6] = bytes; r.info[7] = r.S;
-  } catch (...) { freeAll(); throw; }
-  freeAll();
+  const ReadoutPlan plan = readout_plan(r, 0, 4, false);          // no reduction space; the workgroups are chosen per chunk
+  CallBuffers buf(stream);
+  const size_t nT = (size_t)r.nT, S = (size_t)r.S, Q = (size_t)c.Q;
+  // rows per chunk: what the scratch holds, a multiple of 64, at least 64, at most all rows
+  const int64_t scratch = c.scratchBytes > 0 ? std::min(c.scratchBytes, QT_SCRATCH_DEFAULT) : QT_SCRATCH_DEFAULT;
+  const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(64, scratch / (8 * r.S) / 64 * 64));
+  const int64_t chunks = (r.nT + C - 1) / C;
+  int Sp = 1; while (Sp < r.S) Sp <<= 1;
+  const int R = std::max(1, QT_SORT / Sp);
+  const size_t sortLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT);
+  QuantileDev a{};
+  buf.upload_rows(a, r, P, plan.stageNodes);
+  a.vals = buf.alloc<double>(nullptr, (size_t)C * S);
+  a.probs = buf.alloc(c.probs, Q);
+  a.quantiles = buf.alloc<double>(nullptr, Q * nT);
+  a.Q = c.Q; a.Sp = Sp; a.R = R;
+  if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_predict_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+  HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortLds));
+  for (int64_t ch = 0; ch < chunks; ++ch) {
+    a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0);
+    const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
+    // segments of draws: enough to reach QT_FILL workgroups, each of at least QT_SEG_MIN draws and a multiple of QT_GROUP (a thread's store groups stay whole)
+    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
+    a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
+    const int segs = (int)((r.S + a.segDraws - 1) / a.segDraws);
+    if (plan.staged) hipLaunchKernelGGL(k_predict_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, a);
+    else hipLaunchKernelGGL(k_predict_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, a);
+    HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
+    const int sg = (int)((a.chunkRows + R - 1) / R);
+    hipLaunchKernelGGL(k_row_quantiles, dim3(sg), dim3(QT_BLOCK), sortLds, stream, a);
+    HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
+  }
+  HIP_OK(hipMemcpyAsync(c.quantiles, a.quantiles, Q * nT * 8, hipMemcpyDeviceToHost, stream));
+  HIP_OK(hipStreamSynchronize(stream));
+  r.info[0] = plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = ((int64_t)R << 32) | (int64_t)Sp;
+  r.info[4] = r.maxDrawNodes; r.info[6] = buf.bytes; r.info[7] = r.S;
 }

@@ -1,4 +1,4 @@
-"""s4b_partial_dependence (stan4bart_amd/csrc/dev_pd.inc: k_partial_dependence<staged / global>, k_summary_fold) — the model, the bound, the tree-order
+"""s4b_partial_dependence (stan4bart_amd/csrc/dev_pd.inc over dev_readout.inc: k_partial_dependence<staged / global>, k_summary_fold) — the model, the bound, the tree-order
 restatement and the chains shared by tests/test_partial_dependence.py (CPU) and tests/test_gpu_partial_dependence.py (GPU).
 
 The reference.  For every grid point g the rows get their column(s) `vars` overwritten by the grid point's value(s) and go through predict_bart of the

@@ -1,4 +1,4 @@
-"""s4b_predict_quantiles (stan4bart_amd/csrc/dev_quantile.inc: k_predict_values<staged / global>, k_row_quantiles) — the model and the bound shared
+"""s4b_predict_quantiles (stan4bart_amd/csrc/dev_quantile.inc over dev_readout.inc: k_predict_values<staged / global>, k_row_quantiles) — the model and the bound shared
 by tests/test_predict_quantiles.py (CPU) and tests/test_gpu_predict_quantiles.py (GPU).
 
 The reference is numpy on the FULL [rows x pooled draws] matrix, at shapes where the matrix is small: summary_cases.model(...)["v"] per sampler (the

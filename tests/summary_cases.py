@@ -1,4 +1,4 @@
-"""s4b_predict_summary (stan4bart_amd/csrc/dev_summary.inc: k_predict_summary<staged / global>, k_summary_fold) — the model, the bounds and the
+"""s4b_predict_summary (stan4bart_amd/csrc/dev_summary.inc over dev_readout.inc: k_predict_summary<staged / global>, k_summary_fold) — the model, the bounds and the
 inputs shared by tests/test_predict_summary.py (CPU) and tests/test_gpu_predict_summary.py (GPU).
 
 The reference is numpy on the FULL [rows x draws] matrix, at shapes where the matrix is small: predict_bart of the same sampler supplies the BART fits
