@@ -338,6 +338,50 @@ typedef struct {
 } s4b_quantile_out;
 int S4B_FN(predict_quantiles)(s4b_sampler* s, const s4b_quantile_in* in, s4b_quantile_out* out);
 
+/* extension (R: samples.icate <- (mu.train - mu.test) * (2 z - 1) and its row / column summaries, formed on the device): the PAIRED CONTRAST of two
+ * arms over the same n_test rows and the same draws, pooled over `s` and its peers as predict_quantiles pools them.  For arm a = 1, 0
+ *     z_a(i,k) = bart(x_a[i]; k) + offset_a[i] + sum_j dense_a[i,j] dense_coef[k,j] + sum_e ell_value_a[i,e] ell_coef[k, ell_index_a[i,e]]
+ *     d(i,k)   = v(z_1) - v(z_0),      v = identity (link 0) or Phi (link 1)
+ * The coefficient tables belong to the draw and are shared by the arms; only the row side differs.  `rows` is arm 1 (predict_summary's input, with
+ * the weights: 0 <= n_weights <= 8).  x_test0 is arm 0's predictor matrix, column-major like x_test (NULL: arm 1's); offset0, dense0, ell_index0,
+ * ell_value0 are arm 0's row side of the linear parts, each NULL (arm 1's) or shaped as the arm-1 part; an arm-0 part given where arm 1 has none is
+ * refused.  Both arms are binned with the cut points of `s`; the BART columns whose BINS differ in at least one row — two raw values on the same side
+ * of every cut do not differ — may number at most 2 (more: refused, the message names them).  Trees without a rule on such a column return the same
+ * leaf in both arms: under link 0 they and every linear part whose arm-0 pointer is NULL cancel and are not evaluated at all; under link 1 they are
+ * walked once for both arms.  Both arms go through the same arithmetic and d is (arm 1) - (arm 0): swapping the arms negates d bit for bit.
+ * Outputs, none of which needs more rows-times-draws storage than a chunk's scratch (C x S doubles, C as predict_quantiles chooses it):
+ *   mean[i], m2[i]      mean and sum of squared deviations of d(i, .) over the S pooled draws (two passes; variance m2 / (S - 1)); both or neither
+ *   average[k, g]       sum_i weights[g,i] d(i,k), draw-major over the pooled draws (1 / n_test: the sample average effect; an indicator of the
+ *                       treated over their count: the effect on the treated), rows added in row order within slabs of 64, slabs in order
+ *   quantiles[j, i]     R's type 7 quantiles of d(i, .), 0 <= n_probs <= 16, prob-major
+ * The peer rules, the pooled order, the limit of 16384 pooled draws, scratch_bytes and the query form (all outputs NULL or in = NULL: num_samples of
+ * `s` alone) are predict_quantiles'.  Everything is checked before anything is launched; a refused call leaves info all zero.  Two calls, both routes,
+ * live and stored samplers return the same bits; mean, m2 and quantiles do not depend on the chunking.  Device memory: DESIGN.md 5.8. */
+typedef struct {
+  s4b_summary_in rows;            /* arm 1, the coefficient tables of `s`, the weights */
+  const double* x_test0;          /* n_test x p, or NULL */
+  const double* offset0; const double* dense0; const int32_t* ell_index0; const double* ell_value0;   /* arm 0's row side, each NULL or as in `rows` */
+  int32_t n_probs;                /* 0 .. 16 */
+  const double* probs;
+  int32_t n_peers;
+  s4b_sampler* const* peers;
+  const double* const* peer_dense_coef;
+  const double* const* peer_ell_coef;
+  int64_t scratch_bytes;
+} s4b_contrast_in;
+typedef struct {
+  double* mean; double* m2;       /* n_test each; both or neither */
+  double* average;                /* num_samples x n_weights, draw-major; NULL when n_weights = 0 */
+  double* quantiles;              /* n_probs x n_test, prob-major; NULL when n_probs = 0 */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did: [0] route of the value kernel (1 LDS-staged, 2 global, 0: no tree was walked — link 0 and no affected tree), [1] rows per chunk,
+   * [2] chunks, [3] kernel launches (per chunk: values, + reduce with a per-row output or weights, + fold with weights, + sort with probs),
+   * [4] bytes of device memory the call allocated, [5] pooled draws, [6] D, the differing BART columns, [7] the trees with a rule on one of them:
+   * (the most in one draw) << 32 | (their sum over the pooled draws) */
+  int64_t info[8];
+} s4b_contrast_out;
+int S4B_FN(predict_contrast)(s4b_sampler* s, const s4b_contrast_in* in, s4b_contrast_out* out);
+
 /* The state of a chain BETWEEN TWO GIBBS ITERATIONS as one relocatable byte string: what the next iteration starts from.  It is
  * the hook of the teacher-forced parity tests (state of one implementation injected into the other before every compared
  * transition) and lets a chain continue in another sampler created from the same data; it is not an archive of a fit: the

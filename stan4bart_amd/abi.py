@@ -112,10 +112,22 @@ class QuantileOut(C.Structure):        # s4b_quantile_out
     _fields_ = [("quantiles", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
 
 
+class ContrastIn(C.Structure):         # s4b_contrast_in
+    _fields_ = [("rows", SummaryIn), ("x_test0", c_double_p), ("offset0", c_double_p), ("dense0", c_double_p), ("ell_index0", c_int32_p),
+                ("ell_value0", c_double_p), ("n_probs", C.c_int32), ("probs", c_double_p), ("n_peers", C.c_int32), ("peers", C.POINTER(C.c_void_p)),
+                ("peer_dense_coef", C.POINTER(c_double_p)), ("peer_ell_coef", C.POINTER(c_double_p)), ("scratch_bytes", C.c_int64)]
+
+
+class ContrastOut(C.Structure):        # s4b_contrast_out
+    _fields_ = [("mean", c_double_p), ("m2", c_double_p), ("average", c_double_p), ("quantiles", c_double_p), ("num_samples", C.c_int64),
+                ("info", C.c_int64 * 8)]
+
+
 SUMMARY_ROUTES = {"auto": 0, "staged": 1, "global": 2}
 SUMMARY_INFO = ("route", "rows_per_tile", "workgroups", "staging_bytes", "largest_draw_nodes", "launches", "device_bytes", "staging_nodes")
 PD_INFO = SUMMARY_INFO[:7] + ("largest_affected", "total_affected")          # (the last two share info[7]: trees with a rule on a varied predictor)
 QUANTILE_INFO = ("route", "rows_per_chunk", "chunks", "rows_per_sort", "padded_draws", "largest_draw_nodes", "launches", "device_bytes", "draws")
+CONTRAST_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "differing_columns", "largest_affected", "total_affected")
 PD_GRID_MAX = 64                       # grid points per s4b_partial_dependence call
 
 
@@ -342,6 +354,7 @@ class Sampler:
             "predict_summary": [vp, C.POINTER(SummaryIn), C.POINTER(SummaryOut)],
             "partial_dependence": [vp, C.POINTER(PdIn), C.POINTER(PdOut)],
             "predict_quantiles": [vp, C.POINTER(QuantileIn), C.POINTER(QuantileOut)],
+            "predict_contrast": [vp, C.POINTER(ContrastIn), C.POINTER(ContrastOut)],
             "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
         }
         for name, argtypes in sig.items():
@@ -795,6 +808,81 @@ class Sampler:
         del keep, hold_d, hold_e, buf
         return dict(quantiles=q, draws=int(out.num_samples), info=dict(self.quantile_info))
 
+    def predict_contrast(self, x_test: np.ndarray, x_test0=None, probs=(), peers=(), peer_dense_coef=None, peer_ell_coef=None, offset=None, offset0=None,
+                         dense=None, dense0=None, dense_coef=None, ell_index=None, ell_index0=None, ell_value=None, ell_value0=None, ell_coef=None,
+                         link: int = 0, weights=None, per_row: bool = True, route="auto", stage_nodes: int = 0, scratch_bytes: int = 0) -> dict:
+        """``s4b_predict_contrast``: the paired contrast d = v(arm 1) - v(arm 0) of two arms over the same rows and the same draws, pooled over this
+        sampler and ``peers`` as ``predict_quantiles`` pools them, summarised on the device.  ``x_test`` and the unsuffixed parts are arm 1;
+        ``x_test0``, ``offset0``, ``dense0``, ``ell_index0``, ``ell_value0`` arm 0's row side, each None (arm 1's) or shaped as arm 1's; the
+        coefficient tables are shared by the arms.  At most two BART columns may differ (in their bins).  ``weights`` [G x rows], G <= 8;
+        ``probs`` up to 16; ``per_row`` False leaves mean and m2 out.  Returns dict(mean, m2 [rows] (None without per_row), average [draws x G],
+        quantiles [Q x rows], draws: the pooled count, info: CONTRAST_INFO)."""
+        fn = getattr(self._lib, self._pfx + "predict_contrast", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_contrast")
+
+        def draws(smp):
+            probe = ContrastOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if pr.ndim != 1:
+            raise ValueError(f"probs must be a vector, not shape {pr.shape}")
+        peers = list(peers)
+        own = draws(self)
+        rows_in, keep, rows, G = self._summary_in(own, x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, weights, route,
+                                                   stage_nodes, 0)
+
+        def arm0(a, cols, what, dtype=np.float64):
+            """Arm 0's side of a part: [rows] (cols None) or [rows x cols], column-major; where arm 1 has no such part (cols 0) the array goes
+            through as it is and the library refuses the call."""
+            if a is None:
+                return None
+            a = np.asfortranarray(np.asarray(a, dtype=dtype))
+            want = (rows,) if cols is None else (rows, cols or (a.shape[1] if a.ndim == 2 else 0))
+            if a.shape != want:
+                raise ValueError(f"{what} must have shape {want} like arm 1's, not {a.shape}")
+            return a
+        x0 = arm0(x_test0, keep["x_test"].shape[1], "x_test0")
+        off0 = arm0(offset0, None, "offset0")
+        d0 = arm0(dense0, rows_in.n_dense, "dense0")
+        ix0 = arm0(ell_index0, rows_in.n_ell, "ell_index0", np.int32)
+        ev0 = arm0(ell_value0, rows_in.n_ell, "ell_value0")
+
+        def tables(given, cols, what):          # one C-ordered [peer's draws x cols] table per peer, as an array of pointers
+            if not cols or not peers or given is None:          # (tables missing though needed: the library refuses the call)
+                return None, []
+            if len(given) != len(peers):
+                raise ValueError(f"{what} must hold one table per peer ({len(peers)})")
+            held = []
+            for x, (t, smp) in enumerate(zip(given, peers)):
+                t = np.asarray(t)
+                if t.shape != (draws(smp), cols):
+                    raise ValueError(f"{what}[{x}] must be [{draws(smp)} x {cols}], not shape {t.shape}")
+                held.append(_f64(t, "C"))
+            return (c_double_p * len(held))(*[_dp(t) for t in held]), held
+        pdc, hold_d = tables(peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
+        pec, hold_e = tables(peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
+        handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
+        S = own + sum(draws(p) for p in peers)
+        mean, m2 = (np.zeros(rows), np.zeros(rows)) if per_row else (None, None)
+        avg, q = np.zeros((S, G)), np.zeros((len(pr), rows))
+        spare = np.zeros(1)          # (what a count beyond the library's limits would fill: refused there, which needs a pointer to tell the call from a query)
+        arg = ContrastIn(rows=rows_in, x_test0=_dp(x0), offset0=_dp(off0), dense0=_dp(d0), ell_index0=_ip(ix0), ell_value0=_dp(ev0), n_probs=len(pr),
+                         probs=_dp(pr), n_peers=len(peers), peers=handles if peers else None, peer_dense_coef=pdc, peer_ell_coef=pec,
+                         scratch_bytes=int(scratch_bytes))
+        out = ContrastOut(mean=_dp(mean), m2=_dp(m2), average=_dp(avg) if avg.size else (_dp(spare) if G else None),
+                          quantiles=_dp(q) if q.size else (_dp(spare) if len(pr) else None))
+        if not per_row and not G and not len(pr):
+            out.average = _dp(spare)          # (nothing asked for: the library says so)
+        self.contrast_info = dict(zip(CONTRAST_INFO, [0] * 9))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        w = [int(v) for v in out.info]
+        self.contrast_info = dict(zip(CONTRAST_INFO, w[:7] + [w[7] >> 32, w[7] & 0xFFFFFFFF]))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep, hold_d, hold_e, spare, x0, off0, d0, ix0, ev0
+        return dict(mean=mean, m2=m2, average=avg, quantiles=q, draws=int(out.num_samples), info=dict(self.contrast_info))
+
     def profile_leapfrog(self, n_evals: int = 10) -> dict:
         """Per-leapfrog O(N) sums of the hmc_mode 1 path timed with HIP events (measurement hook of the HIP library)."""
         out = (C.c_double * 8)()
@@ -914,6 +1002,7 @@ class StoredSampler:
     _summary_in = staticmethod(Sampler._summary_in)
     partial_dependence = Sampler.partial_dependence
     predict_quantiles = Sampler.predict_quantiles
+    predict_contrast = Sampler.predict_contrast
     export_bart_state = Sampler.export_bart_state
     get_kept_trees = Sampler.get_kept_trees
     get_kept_trees_indexed = Sampler.get_kept_trees_indexed

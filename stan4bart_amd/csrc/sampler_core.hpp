@@ -97,6 +97,21 @@ struct QuantileCall {
   double* quantiles;                   // [Q x nT], prob-major
 };
 
+// does the device layer form paired contrasts of two arms over the pooled kept draws (s4b_predict_contrast)?  As has_predict_quantiles.
+template <class D, class = void> struct has_predict_contrast : std::false_type {};
+template <class D> struct has_predict_contrast<D, std::void_t<decltype(&D::predict_contrast)>> : std::true_type {};
+// one s4b_predict_contrast call as the device layer sees it: arm 1 as a SummaryCall over the POOLED draws (as QuantileCall.rows; weights, mean, m2,
+// average in use, each NULL where it was not asked for), the D <= 2 BART columns whose bins differ in some row with arm 0's bins of them, arm 0's
+// side of the linear parts that were given (NULL: arm 1's), the tree order of pd_tree_order with vars = the D columns per pooled draw, the probs
+struct ContrastCall {
+  SummaryCall rows;
+  int D, vars[2]; const uint16_t* xb0;                 // [D x nT]
+  const double* offset0; const double* dense0; const int32_t* ellIndex0; const double* ellValue0;
+  const int32_t* order; const int32_t* numBase;        // [S x T], [S]
+  int64_t maxAffected, totalAffected;                  // trees with a rule on a differing column: the most in one draw, the sum over the draws
+  int Q; const double* probs; int64_t scratchBytes; double* quantiles;          // as QuantileCall
+};
+
 template <class Dev>
 class SamplerCore {
  public:
@@ -640,66 +655,100 @@ class SamplerCore {
         if (!(in->probs[j] >= 0.0 && in->probs[j] <= 1.0)) throw std::invalid_argument(who + ": prob " + std::to_string(in->probs[j]) + " outside [0, 1]");
       if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
       const int np = in->n_peers;
-      if (np < 0) throw std::invalid_argument(who + ": negative n_peers");
-      if (np > 0 && (!in->peers || !peers)) throw std::invalid_argument(who + ": n_peers > 0 needs peers");
-      if (np > 0 && rw->n_dense > 0 && !in->peer_dense_coef) throw std::invalid_argument(who + ": n_dense > 0 needs peer_dense_coef, one table per peer");
-      if (np > 0 && rw->n_ell > 0 && !in->peer_ell_coef) throw std::invalid_argument(who + ": n_ell > 0 needs peer_ell_coef, one table per peer");
-      if (own == 0) throw std::invalid_argument(who + ": the sampler holds no kept draws (bart_control.keep_trees, sampling runs)");
-      int64_t S = own;
-      for (int x = 0; x < np; ++x) {
-        const SamplerCore* pc = peers[x];
-        const std::string pw = who + ": peer " + std::to_string(x);
-        if (!pc) throw std::invalid_argument(pw + " is a NULL sampler");
-        if (pc->P_ != P_) throw std::invalid_argument(pw + " has " + std::to_string(pc->P_) + " BART predictors, the sampler " + std::to_string(P_));
-        if (pc->T_ != T_) throw std::invalid_argument(pw + " has " + std::to_string(pc->T_) + " trees per draw, the sampler " + std::to_string(T_));
-        if (pc->binary_ != binary_) throw std::invalid_argument(pw + (pc->binary_ ? " has a binary response, the sampler a continuous one" : " has a continuous response, the sampler a binary one"));
-        for (int j = 0; j < P_; ++j) {
-          const std::vector<double>& ca = cuts_[(size_t)j]; const std::vector<double>& cb = pc->cuts_[(size_t)j];
-          if (ca.size() != cb.size() || (ca.size() && std::memcmp(ca.data(), cb.data(), ca.size() * 8) != 0))
-            throw std::invalid_argument(pw + " has other cut points of predictor " + std::to_string(j) + " than the sampler (the rows are binned once: pooled samplers must share their training predictors)");
-        }
-        const int64_t ps = (int64_t)pc->keptScale_.size() / 2;
-        if (ps == 0) throw std::invalid_argument(pw + " holds no kept draws (bart_control.keep_trees, sampling runs)");
-        if (rw->n_dense > 0 && !in->peer_dense_coef[x]) throw std::invalid_argument(pw + ": n_dense > 0 needs its dense_coef table");
-        if (rw->n_ell > 0 && !in->peer_ell_coef[x]) throw std::invalid_argument(pw + ": n_ell > 0 needs its ell_coef table");
-        S += ps;
-      }
-      if (S > 16384) throw std::invalid_argument(who + ": " + std::to_string(S) + " pooled draws, at most 16384 (one row of the sort as doubles in the LDS of a compute unit)");
+      const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
       const int64_t nT = rw->n_test;
       std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
       bin_matrix(rw->x_test, (size_t)nT, xb);
       QuantileCall c{};
       c.rows = summary_call(rw, xb, own); c.rows.info = out->info; c.rows.G = 0; c.rows.weights = nullptr;
       c.Q = in->n_probs; c.probs = in->probs; c.scratchBytes = in->scratch_bytes; c.quantiles = out->quantiles;
-      // the pool: this sampler's draws, then the peers' in their order; tree starts rebased onto the concatenated nodes
-      std::vector<PackedNode> nodes; std::vector<int64_t> treeStart; std::vector<double> scale, denseCoef, ellCoef;
-      if (np > 0) {
-        const size_t M = (size_t)rw->n_dense, q = rw->n_ell > 0 ? (size_t)rw->n_ell_coef : 0;
-        size_t numNodes = keptNodes_.size();
-        for (int x = 0; x < np; ++x) numNodes += peers[x]->keptNodes_.size();
-        nodes.reserve(numNodes); treeStart.reserve((size_t)S * (size_t)T_); scale.reserve((size_t)S * 2);
-        denseCoef.reserve((size_t)S * M); ellCoef.reserve((size_t)S * q);
-        for (int x = -1; x < np; ++x) {
-          const SamplerCore* pc = x < 0 ? this : peers[x];
-          const size_t ps = pc->keptScale_.size() / 2;
-          const int64_t base = (int64_t)nodes.size();
-          for (int64_t st : pc->keptTreeStart_) treeStart.push_back(st + base);
-          nodes.insert(nodes.end(), pc->keptNodes_.begin(), pc->keptNodes_.end());
-          scale.insert(scale.end(), pc->keptScale_.begin(), pc->keptScale_.end());
-          const double* dc = x < 0 ? rw->dense_coef : in->peer_dense_coef ? in->peer_dense_coef[x] : nullptr;
-          const double* ec = x < 0 ? rw->ell_coef : in->peer_ell_coef ? in->peer_ell_coef[x] : nullptr;
-          if (M) denseCoef.insert(denseCoef.end(), dc, dc + ps * M);
-          if (q) ellCoef.insert(ellCoef.end(), ec, ec + ps * q);
-          c.rows.maxDrawNodes = std::max(c.rows.maxDrawNodes, pc->summary_call(rw, xb, (int64_t)ps).maxDrawNodes);
-        }
-        c.rows.nodes = nodes.data(); c.rows.numNodes = nodes.size(); c.rows.treeStart = treeStart.data(); c.rows.scale = scale.data(); c.rows.S = S;
-        if (M) c.rows.denseCoef = denseCoef.data();
-        if (q) c.rows.ellCoef = ellCoef.data();
-      }
+      DrawPool pool;
+      pool_concat(c.rows, pool, rw, xb, np, peers, in->peer_dense_coef, in->peer_ell_coef, S);
       dev_.predict_quantiles(c);
       out->num_samples = S;
       return S;
     } else throw std::invalid_argument("predict_quantiles: this device layer has no quantile kernels (the quantiles are formed by the HIP library only)");
+  }
+  // s4b_predict_contrast: the paired contrast d(i,k) = v(z_1) - v(z_0) of two arms over the same rows and the same pooled draws, summarised on the
+  // device (mean, m2 and quantiles per row, weighted row sums per draw).  The arms are binned with this sampler's cut points; the BART columns whose
+  // BINS differ in some row (at most two) are the only ones of arm 0 that travel.  Pooled like predict_quantiles.  Everything is validated here,
+  // before any launch.
+  int64_t predict_contrast(const s4b_contrast_in* in, s4b_contrast_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_contrast: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in || (!out->mean && !out->m2 && !out->average && !out->quantiles)) return own;          // query
+    if constexpr (has_predict_contrast<Dev>::value) {
+      const std::string who = "predict_contrast";
+      const s4b_summary_in* rw = &in->rows;
+      check_summary_rows(rw, who, 8);
+      if (in->n_probs < 0 || in->n_probs > 16) throw std::invalid_argument(who + ": between 0 and 16 probs per call, not " + std::to_string(in->n_probs));
+      if (in->n_probs > 0 && !in->probs) throw std::invalid_argument(who + ": NULL probs");
+      for (int j = 0; j < in->n_probs; ++j)
+        if (!(in->probs[j] >= 0.0 && in->probs[j] <= 1.0)) throw std::invalid_argument(who + ": prob " + std::to_string(in->probs[j]) + " outside [0, 1]");
+      if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
+      if ((out->mean == nullptr) != (out->m2 == nullptr)) throw std::invalid_argument(who + ": mean and m2 are given together or not at all");
+      if (rw->n_weights > 0 && !out->average) throw std::invalid_argument(who + ": n_weights > 0 needs average");
+      if (in->n_probs > 0 && !out->quantiles) throw std::invalid_argument(who + ": n_probs > 0 needs quantiles");
+      if (!out->mean && rw->n_weights == 0 && in->n_probs == 0) throw std::invalid_argument(who + ": nothing asked for (no per-row output, no weights, no probs)");
+      const int64_t nT = rw->n_test;
+      // arm 0: a part of its own only where arm 1 has that part
+      if (in->offset0 && !rw->offset) throw std::invalid_argument(who + ": offset0 given, but arm 1 has no offset");
+      if (in->dense0 && rw->n_dense == 0) throw std::invalid_argument(who + ": dense0 given, but arm 1 has no dense part (n_dense = 0)");
+      if ((in->ell_index0 || in->ell_value0) && rw->n_ell == 0) throw std::invalid_argument(who + ": ell_index0 / ell_value0 given, but arm 1 has no ELL part (n_ell = 0)");
+      if (in->ell_index0)
+        for (size_t x = 0, m = (size_t)nT * (size_t)rw->n_ell; x < m; ++x)
+          if (in->ell_index0[x] < -1 || in->ell_index0[x] >= rw->n_ell_coef)
+            throw std::invalid_argument(who + ": ell_index0 " + std::to_string(in->ell_index0[x]) + " outside [-1, " + std::to_string(rw->n_ell_coef) + ")");
+      if (in->x_test0)
+        for (size_t x = 0, m = (size_t)nT * (size_t)P_; x < m; ++x) if (std::isnan(in->x_test0[x])) throw std::invalid_argument(who + ": x_test0 holds a NaN");
+      const int np = in->n_peers;
+      const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
+      std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
+      bin_matrix(rw->x_test, (size_t)nT, xb);
+      // the differing columns: those whose BINS differ in at least one row (two raw values on the same side of every cut do not differ)
+      std::vector<int32_t> diff;
+      std::vector<uint16_t> xb0;
+      if (in->x_test0) {
+        std::vector<uint16_t> all((size_t)P_ * (size_t)nT);
+        bin_matrix(in->x_test0, (size_t)nT, all);
+        for (int j = 0; j < P_; ++j)
+          if (std::memcmp(all.data() + (size_t)j * (size_t)nT, xb.data() + (size_t)j * (size_t)nT, (size_t)nT * 2) != 0) diff.push_back(j);
+        if (diff.size() > 2) {
+          std::string cols;
+          for (int32_t j : diff) cols += (cols.empty() ? "" : ", ") + std::to_string(j);
+          throw std::invalid_argument(who + ": the arms differ in " + std::to_string(diff.size()) + " BART columns (" + cols + "), at most 2 are supported");
+        }
+        for (int32_t j : diff) xb0.insert(xb0.end(), all.begin() + (size_t)j * (size_t)nT, all.begin() + (size_t)(j + 1) * (size_t)nT);
+      }
+      ContrastCall c{};
+      c.rows = summary_call(rw, xb, own); c.rows.info = out->info;
+      c.rows.mean = out->mean; c.rows.m2 = out->m2; c.rows.average = out->average;
+      c.D = (int)diff.size(); c.vars[0] = c.D > 0 ? diff[0] : -1; c.vars[1] = c.D > 1 ? diff[1] : -1; c.xb0 = xb0.data();
+      c.offset0 = in->offset0; c.dense0 = in->dense0; c.ellIndex0 = in->ell_index0; c.ellValue0 = in->ell_value0;
+      c.Q = in->n_probs; c.probs = in->probs; c.scratchBytes = in->scratch_bytes; c.quantiles = out->quantiles;
+      DrawPool pool;
+      pool_concat(c.rows, pool, rw, xb, np, peers, in->peer_dense_coef, in->peer_ell_coef, S);
+      // the tree order of every pooled draw, each sampler's own trees: pd_tree_order with vars = the differing columns (none: nothing is affected)
+      std::vector<int32_t> order, numBase;
+      if (c.D == 0) {
+        order.resize((size_t)(S * T_)); numBase.assign((size_t)S, T_);
+        for (int64_t k = 0; k < S; ++k) for (int t = 0; t < T_; ++t) order[(size_t)(k * T_ + t)] = t;
+      } else {
+        std::vector<int32_t> o, nb;
+        for (int x = -1; x < np; ++x) {
+          int64_t mx = 0, tot = 0;
+          (x < 0 ? this : peers[x])->pd_tree_order(c.D, c.vars, o, nb, mx, tot);
+          order.insert(order.end(), o.begin(), o.end()); numBase.insert(numBase.end(), nb.begin(), nb.end());
+          c.maxAffected = std::max(c.maxAffected, mx); c.totalAffected += tot;
+        }
+      }
+      c.order = order.data(); c.numBase = numBase.data();
+      dev_.predict_contrast(c);
+      out->num_samples = S;
+      return S;
+    } else throw std::invalid_argument("predict_contrast: this device layer has no contrast kernels (the contrasts are formed by the HIP library only)");
   }
   // ---- sampler state as a byte string (layout: include/stan4bart_amd.h, s4b_get_state)
   int64_t get_state(void* buf, int64_t cap) {
@@ -1052,6 +1101,66 @@ class SamplerCore {
       cuts_[(size_t)j].resize((size_t)m);
       for (int c = 0; c < m; ++c) cuts_[(size_t)j][(size_t)c] = mn + (double)(c + 1) * (mx - mn) / (double)(m + 1);
     }
+  }
+  // ---- pooling of several samplers' kept draws into one call (s4b_predict_quantiles, s4b_predict_contrast)
+  // the peer rules, checked before anything is launched: returns the pooled draw count S (this sampler's draws, then the peers')
+  int64_t pool_check(const std::string& who, const s4b_summary_in* rw, int np, bool havePeers, const SamplerCore* const* peers, const double* const* peerDenseCoef,
+                     const double* const* peerEllCoef) const {
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    if (np < 0) throw std::invalid_argument(who + ": negative n_peers");
+    if (np > 0 && (!havePeers || !peers)) throw std::invalid_argument(who + ": n_peers > 0 needs peers");
+    if (np > 0 && rw->n_dense > 0 && !peerDenseCoef) throw std::invalid_argument(who + ": n_dense > 0 needs peer_dense_coef, one table per peer");
+    if (np > 0 && rw->n_ell > 0 && !peerEllCoef) throw std::invalid_argument(who + ": n_ell > 0 needs peer_ell_coef, one table per peer");
+    if (own == 0) throw std::invalid_argument(who + ": the sampler holds no kept draws (bart_control.keep_trees, sampling runs)");
+    int64_t S = own;
+    for (int x = 0; x < np; ++x) {
+      const SamplerCore* pc = peers[x];
+      const std::string pw = who + ": peer " + std::to_string(x);
+      if (!pc) throw std::invalid_argument(pw + " is a NULL sampler");
+      if (pc->P_ != P_) throw std::invalid_argument(pw + " has " + std::to_string(pc->P_) + " BART predictors, the sampler " + std::to_string(P_));
+      if (pc->T_ != T_) throw std::invalid_argument(pw + " has " + std::to_string(pc->T_) + " trees per draw, the sampler " + std::to_string(T_));
+      if (pc->binary_ != binary_) throw std::invalid_argument(pw + (pc->binary_ ? " has a binary response, the sampler a continuous one" : " has a continuous response, the sampler a binary one"));
+      for (int j = 0; j < P_; ++j) {
+        const std::vector<double>& ca = cuts_[(size_t)j]; const std::vector<double>& cb = pc->cuts_[(size_t)j];
+        if (ca.size() != cb.size() || (ca.size() && std::memcmp(ca.data(), cb.data(), ca.size() * 8) != 0))
+          throw std::invalid_argument(pw + " has other cut points of predictor " + std::to_string(j) + " than the sampler (the rows are binned once: pooled samplers must share their training predictors)");
+      }
+      const int64_t ps = (int64_t)pc->keptScale_.size() / 2;
+      if (ps == 0) throw std::invalid_argument(pw + " holds no kept draws (bart_control.keep_trees, sampling runs)");
+      if (rw->n_dense > 0 && !peerDenseCoef[x]) throw std::invalid_argument(pw + ": n_dense > 0 needs its dense_coef table");
+      if (rw->n_ell > 0 && !peerEllCoef[x]) throw std::invalid_argument(pw + ": n_ell > 0 needs its ell_coef table");
+      S += ps;
+    }
+    if (S > 16384) throw std::invalid_argument(who + ": " + std::to_string(S) + " pooled draws, at most 16384 (one row of the sort as doubles in the LDS of a compute unit)");
+    return S;
+  }
+  // the pool itself: this sampler's draws, then the peers' in their order; tree starts rebased onto the concatenated nodes.  `rows` (a summary_call of
+  // this sampler alone) is pointed at the pool's storage, which must outlive the device call; without peers it stays as it is.
+  struct DrawPool { std::vector<PackedNode> nodes; std::vector<int64_t> treeStart; std::vector<double> scale, denseCoef, ellCoef; };
+  void pool_concat(SummaryCall& rows, DrawPool& pool, const s4b_summary_in* rw, const std::vector<uint16_t>& xb, int np, const SamplerCore* const* peers,
+                   const double* const* peerDenseCoef, const double* const* peerEllCoef, int64_t S) const {
+    if (np <= 0) return;
+    const size_t M = (size_t)rw->n_dense, q = rw->n_ell > 0 ? (size_t)rw->n_ell_coef : 0;
+    size_t numNodes = keptNodes_.size();
+    for (int x = 0; x < np; ++x) numNodes += peers[x]->keptNodes_.size();
+    pool.nodes.reserve(numNodes); pool.treeStart.reserve((size_t)S * (size_t)T_); pool.scale.reserve((size_t)S * 2);
+    pool.denseCoef.reserve((size_t)S * M); pool.ellCoef.reserve((size_t)S * q);
+    for (int x = -1; x < np; ++x) {
+      const SamplerCore* pc = x < 0 ? this : peers[x];
+      const size_t ps = pc->keptScale_.size() / 2;
+      const int64_t base = (int64_t)pool.nodes.size();
+      for (int64_t st : pc->keptTreeStart_) pool.treeStart.push_back(st + base);
+      pool.nodes.insert(pool.nodes.end(), pc->keptNodes_.begin(), pc->keptNodes_.end());
+      pool.scale.insert(pool.scale.end(), pc->keptScale_.begin(), pc->keptScale_.end());
+      const double* dc = x < 0 ? rw->dense_coef : peerDenseCoef ? peerDenseCoef[x] : nullptr;
+      const double* ec = x < 0 ? rw->ell_coef : peerEllCoef ? peerEllCoef[x] : nullptr;
+      if (M) pool.denseCoef.insert(pool.denseCoef.end(), dc, dc + ps * M);
+      if (q) pool.ellCoef.insert(pool.ellCoef.end(), ec, ec + ps * q);
+      rows.maxDrawNodes = std::max(rows.maxDrawNodes, pc->summary_call(rw, xb, (int64_t)ps).maxDrawNodes);
+    }
+    rows.nodes = pool.nodes.data(); rows.numNodes = pool.nodes.size(); rows.treeStart = pool.treeStart.data(); rows.scale = pool.scale.data(); rows.S = S;
+    if (M) rows.denseCoef = pool.denseCoef.data();
+    if (q) rows.ellCoef = pool.ellCoef.data();
   }
   // what s4b_predict_summary and s4b_partial_dependence check of their rows (s4b_summary_in) before anything is launched
   void check_summary_rows(const s4b_summary_in* in, const std::string& who, int maxWeights) const {

@@ -517,6 +517,96 @@ class Stan4bartFit:
                                                peer_ell_coef=None if first["ell_index"] is None else [a["ell_coef"] for a in others], **first)
         return {"probs": pr, "quantiles": r["quantiles"], "draws": r["draws"]}
 
+    # ------------------------------------------------------------------ predict_contrast
+    def predict_contrast(self, x_bart=None, x_bart0=None, X=None, X0=None, groups: Optional[Sequence[GroupTerm]] = None,
+                         groups0: Optional[Sequence[GroupTerm]] = None, offset=None, offset0=None, treatment=None, levels=(1.0, 0.0), type: str = "ev",
+                         row_weights=None, probs=(0.025, 0.5, 0.975), combine_chains: bool = True, sample_new_levels: bool = True,
+                         seed: Optional[int] = None):
+        """Per-row treatment effects — ``(predict(arm 1) - predict(arm 0))`` of the same rows under the same draws, the reference's
+        ``samples.icate`` — summarised on the device without either [rows x draws] matrix, in ONE pooled call (``s4b_predict_contrast``: the first
+        chain's sampler with the others as its peers).  Arm 1 is ``x_bart``, ``X``, ``groups``, ``offset``; arm 0 the arguments with suffix 0,
+        each None for arm 1's.  ``treatment=("x_bart" | "X", column)`` builds both arms from the one row set given, the column set to
+        ``levels[0]`` in arm 1 and ``levels[1]`` in arm 0 (slopes of ``groups`` are not touched: hand random slopes on the treatment in as explicit
+        arms).  The arms may differ in at most two BART columns.  The random parts of both arms share one coefficient table and one draw of every
+        unseen level.  ``type`` "ev" or "indiv.bart".  ``row_weights`` [G x rows], G <= 8 (None: 1 / rows, the sample average effect).
+        Returns ``mean`` and ``sd`` (ddof 1) per row, ``average`` [G, draws] ([G, iter, chain] with ``combine_chains=False``), ``probs``,
+        ``quantiles`` [Q, rows] and ``draws``."""
+        if type == "ppd":
+            raise ValueError("predict_contrast does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("predict_contrast requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_contrast needs x_bart, the new rows of the BART predictors")
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or len(pr) > 16 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of at most 16 values in [0, 1], not {probs!r}")
+        x_bart = np.asarray(x_bart, dtype=np.float64)
+        rows = x_bart.shape[0]
+        if treatment is not None:
+            if any(a is not None for a in (x_bart0, X0, groups0, offset0)):
+                raise ValueError("'treatment' builds both arms from one row set: no explicit arm-0 argument (x_bart0, X0, groups0, offset0) beside it")
+            if not (isinstance(treatment, (tuple, list)) and len(treatment) == 2 and treatment[0] in ("x_bart", "X")) or len(levels) != 2:
+                raise ValueError(f"'treatment' must be (\"x_bart\" | \"X\", column) and 'levels' a pair, not {treatment!r}, {levels!r}")
+            where, col = treatment[0], int(treatment[1])
+            src = x_bart if where == "x_bart" else (None if X is None else np.asarray(X, dtype=np.float64).reshape(rows, -1))
+            if src is None or not 0 <= col < src.shape[1]:
+                raise ValueError(f"'treatment' names column {col} of {where}, which is not there")
+            arm1, arm0 = src.copy(), src.copy()
+            arm1[:, col], arm0[:, col] = float(levels[0]), float(levels[1])
+            if where == "x_bart":
+                x_bart, x_bart0 = arm1, arm0
+            else:
+                X, X0 = arm1, arm0
+        if row_weights is None:
+            w = np.full((1, rows), 1.0 / rows)
+        else:
+            w = np.asarray(row_weights, dtype=np.float64)
+            if w.ndim != 2 or w.shape[1] != rows:
+                raise ValueError(f"row_weights must have shape [G, {rows}], not {w.shape}")
+            if not 1 <= w.shape[0] <= 8:
+                raise ValueError(f"row_weights holds {w.shape[0]} weight vectors: between 1 and 8 per call")
+        ev = type == "ev"
+        if ev and X0 is not None and X is None:
+            raise ValueError("X0 given without X")
+        if ev and groups0 is not None and len(groups0) and not (groups is not None and len(groups)):
+            raise ValueError("groups0 given without groups")
+        if ev and offset0 is not None and offset is None:
+            raise ValueError("offset0 given without offset")
+        n_fixef, n_terms, n_chain = len(self._rows("beta.")), len(self.terms), len(self.samplers)
+        kw = dict(link=1 if (ev and self.family == "binomial") else 0, offset=offset if ev else None, offset0=offset0 if ev else None)
+        dense_coef = ell_coef = None
+        if ev and X is not None and n_fixef:          # the fixed part: the arms' rows against the one table of the chain
+            beta = self.stan[self._rows("beta.")]                    # [K, iter, chain]
+            dense_coef = [np.ascontiguousarray(beta[:, :, c].T) for c in range(n_chain)]
+            kw.update(dense=np.asarray(X, dtype=np.float64).reshape(-1, n_fixef) - self.X_means, dense_coef=dense_coef[0],
+                      dense0=None if X0 is None else np.asarray(X0, dtype=np.float64).reshape(-1, n_fixef) - self.X_means)
+        if ev and groups is not None and len(groups) and n_terms:
+            # the random parts of both arms through ONE _ell_random call on the stacked rows: one coefficient table, one draw of every unseen level
+            terms, two = {g.name: g for g in groups}, groups0 is not None and len(groups0) > 0
+            if two:
+                by0 = {g.name: g for g in groups0}
+                if sorted(by0) != sorted(terms):
+                    raise ValueError("groups0 must name the grouping terms of groups")
+                terms = {name: GroupTerm(np.concatenate([np.asarray(g.levels), np.asarray(by0[name].levels)]),
+                                         None if g.slopes is None else np.vstack([np.asarray(g.slopes, dtype=np.float64).reshape(rows, -1),
+                                                                                  np.asarray(by0[name].slopes, dtype=np.float64).reshape(rows, -1)]), name)
+                         for name, g in terms.items()}
+            ix, val, ell_coef = self._ell_random([terms[g.name] for g in self.terms if g.name in terms], sample_new_levels, np.random.default_rng(seed))
+            kw.update(ell_index=ix[:rows], ell_value=val[:rows], ell_coef=ell_coef[0])
+            if two:
+                kw.update(ell_index0=ix[rows:], ell_value0=val[rows:])
+        r = self.samplers[0].predict_contrast(x_bart, None if x_bart0 is None else np.asarray(x_bart0, dtype=np.float64), probs=pr, peers=self.samplers[1:],
+                                              peer_dense_coef=None if dense_coef is None else dense_coef[1:],
+                                              peer_ell_coef=None if ell_coef is None else ell_coef[1:], weights=w, **kw)
+        n = r["draws"]
+        sd = np.sqrt(r["m2"] / (n - 1)) if n > 1 else np.full(rows, np.nan)
+        average = r["average"].T                                     # [G, pooled draws], chain after chain
+        if not combine_chains:
+            average = average.reshape(w.shape[0], len(self.samplers), -1).transpose(0, 2, 1)
+        return {"mean": r["mean"], "sd": sd, "average": average, "probs": pr, "quantiles": r["quantiles"], "draws": n}
+
     def export_bart_states(self) -> list:
         """``stan4bart_exportBARTState`` per chain (reference R/stan4bart_fit.R:572-580): byte strings that
         ``attach_stored_samplers`` turns back into predict-capable samplers, in this or another process."""
