@@ -382,6 +382,60 @@ typedef struct {
 } s4b_contrast_out;
 int S4B_FN(predict_contrast)(s4b_sampler* s, const s4b_contrast_in* in, s4b_contrast_out* out);
 
+/* extension (R: quantiles and scores of extract(fit, "ppd") against held-out responses, formed on the device): the POSTERIOR PREDICTIVE read-out per row
+ * over the draws of `s` and its peers, pooled as predict_quantiles pools them: prediction intervals for NEW OBSERVATIONS and the scores of held-out
+ * responses y, without the rows-times-draws matrix.  Row i is a row of the call; k is the pooled draw index (the draws of `s`, then the peers' in peer
+ * order); z(i,k) is predict_summary's z, the same additions in the same order.  `rows` is predict_summary's input with n_weights 0; rows.link names
+ * the RESPONSE here: 0 continuous, 1 binary (probit).
+ *   link 0   sd(i,k) = sigma[k] row_scale[i].  sigma holds one value per draw of `s`, peer_sigma[x] one per draw of peer x, each finite and > 0;
+ *            row_scale has n_test values, finite and >= 0 (and > 0 when y is given), or is NULL: 1 (a fit with observation weights w passes
+ *            1 / sqrt(w): the reference's sigma sqrt(1 / w)).
+ *            y_rep(i,k) = z + sd e(i,k),   e(i,k) = sqrt(-2 log u1) cos(2 pi u2),   u1, u2 the two (0, 1] uniforms (53 bits each) of ONE block
+ *            philox4x32_10({i low, i high, k, 0x50504431}, noise_key low, noise_key high).  The last counter word is a fixed tag ("PPD1") that no
+ *            counter of the parallel probit latents carries (theirs is an attempt number below 4096), so the blocks differ even under one key.
+ *            e is a pure function of (noise_key, i, k): chunking, route, scratch_bytes, live or stored samplers cannot change a bit of the result.
+ *            quantiles[j, i]: R's type 7 of y_rep(i, .), 0 <= n_probs <= 16, prob-major.
+ *            l(i,k) = -log(2 pi) / 2 - log sd - r^2 / 2,   r = (y_i - z) / sd
+ *   link 1   no y_rep is formed: the predictive distribution of a row is Bernoulli(mean of ev), which predict_summary gives.  n_probs > 0 is refused.
+ *            l(i,k) = log Phi(z) where y_i = 1, log Phi(-z) where y_i = 0 (the logarithm of Phi at the signed argument); every y is exactly 0 or 1;
+ *            sigma, peer_sigma and row_scale are not read.
+ * Scores, only when y (n_test values, finite) is given, S the pooled draw count:
+ *   lpd[i]              m + log(sum_k exp(l - m)) - log S,  m = max_k l: the log pointwise predictive density
+ *   lmean[i], lm2[i]    mean and sum of squared deviations of l(i, .) in two passes; both or neither.  The WAIC penalty is lm2 / (S - 1)
+ *   pit[i]              (1 / S) sum_k Phi(r(i,k)); link 0 only: it must be NULL under link 1
+ * A call that asks for nothing (no probs, no y with a score output) is refused.  The peer rules, the pooled order, the limit of 16384 pooled draws,
+ * scratch_bytes, the rows per chunk and the query form (all outputs NULL or in = NULL: num_samples of `s` alone) are predict_quantiles'.  Everything
+ * is checked before anything is launched; a refused call leaves info all zero.  Two calls return the same bits.  The draw reductions use a fixed
+ * tree in pooled order and no floating-point atomics: a PERMUTED POOL may change the last bits of the scores, and it moves the noise (e belongs to
+ * the pooled index k), so the quantiles of a permuted pool are those of another draw of the noise.  Device memory: DESIGN.md 5.9. */
+typedef struct {
+  s4b_summary_in rows;            /* n_weights 0; link: the response, 0 continuous, 1 binary */
+  const double* y;                /* n_test held-out responses, or NULL: no scores */
+  const double* sigma;            /* one per draw of `s` (link 0) */
+  const double* row_scale;        /* n_test, or NULL: 1 */
+  uint64_t noise_key;
+  int32_t n_probs;                /* 0 .. 16; 0 under link 1 */
+  const double* probs;
+  int32_t n_peers;
+  s4b_sampler* const* peers;
+  const double* const* peer_dense_coef;
+  const double* const* peer_ell_coef;
+  const double* const* peer_sigma;        /* [n_peers] vectors (one value per draw of that peer), link 0 */
+  int64_t scratch_bytes;
+} s4b_ppd_in;
+typedef struct {
+  double* quantiles;              /* n_probs x n_test, prob-major; NULL when n_probs = 0 */
+  double* lpd;                    /* n_test, or NULL */
+  double* lmean; double* lm2;     /* n_test each; both or neither */
+  double* pit;                    /* n_test, or NULL; NULL under link 1 */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did, as s4b_quantile_out.info: [0] route of the value kernel (1 LDS-staged, 2 global; 0: nothing was launched), [1] rows per chunk C,
+   * [2] chunks, [3] (rows per workgroup of k_ppd_rows) << 32 | draws padded to a power of two, [4] nodes of the largest pooled draw, [5] kernel
+   * launches (2 per chunk), [6] bytes of device memory the call allocated, [7] pooled draws */
+  int64_t info[8];
+} s4b_ppd_out;
+int S4B_FN(predict_ppd)(s4b_sampler* s, const s4b_ppd_in* in, s4b_ppd_out* out);
+
 /* The state of a chain BETWEEN TWO GIBBS ITERATIONS as one relocatable byte string: what the next iteration starts from.  It is
  * the hook of the teacher-forced parity tests (state of one implementation injected into the other before every compared
  * transition) and lets a chain continue in another sampler created from the same data; it is not an archive of a fit: the

@@ -123,12 +123,41 @@ class ContrastOut(C.Structure):        # s4b_contrast_out
                 ("info", C.c_int64 * 8)]
 
 
+class PpdIn(C.Structure):              # s4b_ppd_in
+    _fields_ = [("rows", SummaryIn), ("y", c_double_p), ("sigma", c_double_p), ("row_scale", c_double_p), ("noise_key", C.c_uint64),
+                ("n_probs", C.c_int32), ("probs", c_double_p), ("n_peers", C.c_int32), ("peers", C.POINTER(C.c_void_p)),
+                ("peer_dense_coef", C.POINTER(c_double_p)), ("peer_ell_coef", C.POINTER(c_double_p)), ("peer_sigma", C.POINTER(c_double_p)),
+                ("scratch_bytes", C.c_int64)]
+
+
+class PpdOut(C.Structure):             # s4b_ppd_out
+    _fields_ = [("quantiles", c_double_p), ("lpd", c_double_p), ("lmean", c_double_p), ("lm2", c_double_p), ("pit", c_double_p),
+                ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
 SUMMARY_ROUTES = {"auto": 0, "staged": 1, "global": 2}
 SUMMARY_INFO = ("route", "rows_per_tile", "workgroups", "staging_bytes", "largest_draw_nodes", "launches", "device_bytes", "staging_nodes")
 PD_INFO = SUMMARY_INFO[:7] + ("largest_affected", "total_affected")          # (the last two share info[7]: trees with a rule on a varied predictor)
 QUANTILE_INFO = ("route", "rows_per_chunk", "chunks", "rows_per_sort", "padded_draws", "largest_draw_nodes", "launches", "device_bytes", "draws")
 CONTRAST_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "differing_columns", "largest_affected", "total_affected")
+PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
 PD_GRID_MAX = 64                       # grid points per s4b_partial_dependence call
+
+
+def _peer_tables(peers, draws, given, cols, what):
+    """One C-ordered [peer's draws x cols] table per peer of a pooled call, as an array of pointers: (the array or None, the tables it points into).
+    `draws(sampler)` is the peer's kept draw count."""
+    if not cols or not peers or given is None:          # (tables missing though needed: the library refuses the call)
+        return None, []
+    if len(given) != len(peers):
+        raise ValueError(f"{what} must hold one table per peer ({len(peers)})")
+    held = []
+    for x, (t, smp) in enumerate(zip(given, peers)):
+        t = np.asarray(t)
+        if t.shape != (draws(smp), cols):
+            raise ValueError(f"{what}[{x}] must be [{draws(smp)} x {cols}], not shape {t.shape}")
+        held.append(_f64(t, "C"))
+    return (c_double_p * len(held))(*[_dp(t) for t in held]), held
 
 
 def _dp(a: Optional[np.ndarray]):
@@ -355,6 +384,7 @@ class Sampler:
             "partial_dependence": [vp, C.POINTER(PdIn), C.POINTER(PdOut)],
             "predict_quantiles": [vp, C.POINTER(QuantileIn), C.POINTER(QuantileOut)],
             "predict_contrast": [vp, C.POINTER(ContrastIn), C.POINTER(ContrastOut)],
+            "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
             "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
         }
         for name, argtypes in sig.items():
@@ -780,20 +810,8 @@ class Sampler:
         rows_in, keep, rows, _ = self._summary_in(draws(self), x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, None, route,
                                                    stage_nodes, 0)
 
-        def tables(given, cols, what):          # one C-ordered [peer's draws x cols] table per peer, as an array of pointers
-            if not cols or not peers or given is None:          # (tables missing though needed: the library refuses the call)
-                return None, []
-            if len(given) != len(peers):
-                raise ValueError(f"{what} must hold one table per peer ({len(peers)})")
-            held = []
-            for x, (t, smp) in enumerate(zip(given, peers)):
-                t = np.asarray(t)
-                if t.shape != (draws(smp), cols):
-                    raise ValueError(f"{what}[{x}] must be [{draws(smp)} x {cols}], not shape {t.shape}")
-                held.append(_f64(t, "C"))
-            return (c_double_p * len(held))(*[_dp(t) for t in held]), held
-        pdc, hold_d = tables(peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
-        pec, hold_e = tables(peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
+        pdc, hold_d = _peer_tables(peers, draws, peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
+        pec, hold_e = _peer_tables(peers, draws, peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
         handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
         q = np.zeros((len(pr), rows))
         buf = q if q.size else np.zeros(1)          # (no prob: refused by the library, which needs a pointer to tell the call from a query)
@@ -849,20 +867,8 @@ class Sampler:
         ix0 = arm0(ell_index0, rows_in.n_ell, "ell_index0", np.int32)
         ev0 = arm0(ell_value0, rows_in.n_ell, "ell_value0")
 
-        def tables(given, cols, what):          # one C-ordered [peer's draws x cols] table per peer, as an array of pointers
-            if not cols or not peers or given is None:          # (tables missing though needed: the library refuses the call)
-                return None, []
-            if len(given) != len(peers):
-                raise ValueError(f"{what} must hold one table per peer ({len(peers)})")
-            held = []
-            for x, (t, smp) in enumerate(zip(given, peers)):
-                t = np.asarray(t)
-                if t.shape != (draws(smp), cols):
-                    raise ValueError(f"{what}[{x}] must be [{draws(smp)} x {cols}], not shape {t.shape}")
-                held.append(_f64(t, "C"))
-            return (c_double_p * len(held))(*[_dp(t) for t in held]), held
-        pdc, hold_d = tables(peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
-        pec, hold_e = tables(peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
+        pdc, hold_d = _peer_tables(peers, draws, peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
+        pec, hold_e = _peer_tables(peers, draws, peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
         handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
         S = own + sum(draws(p) for p in peers)
         mean, m2 = (np.zeros(rows), np.zeros(rows)) if per_row else (None, None)
@@ -882,6 +888,67 @@ class Sampler:
         self._check(rc)
         del keep, hold_d, hold_e, spare, x0, off0, d0, ix0, ev0
         return dict(mean=mean, m2=m2, average=avg, quantiles=q, draws=int(out.num_samples), info=dict(self.contrast_info))
+
+    def predict_ppd(self, x_test: np.ndarray, probs=(), y=None, sigma=None, row_scale=None, noise_key: int = 0, peers=(), peer_sigma=None,
+                    peer_dense_coef=None, peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None, ell_coef=None,
+                    link: int = 0, lpd: bool = True, moments: bool = True, pit: Optional[bool] = None, route="auto", stage_nodes: int = 0,
+                    scratch_bytes: int = 0) -> dict:
+        """``s4b_predict_ppd``: the posterior predictive read-out per row over the kept draws of this sampler and of ``peers``, pooled in ONE device
+        call as ``predict_quantiles`` pools them.  ``link`` names the response: 0 continuous, 1 binary.  Link 0: ``sigma`` [this sampler's draws]
+        and ``peer_sigma`` (one vector per peer), ``row_scale`` [rows] or None (1); ``probs`` (up to 16, may be empty) gives the type-7 quantiles
+        of y_rep = z + sigma row_scale e with e a pure function of (``noise_key``, row, pooled draw).  With ``y`` [rows] the scores: ``lpd``,
+        ``moments`` (lmean and lm2 of the pointwise log-likelihood) and ``pit`` (None: under link 0 only), each left out where False.  The other
+        arguments as ``predict_quantiles`` takes them.  Returns dict(quantiles [Q x rows], lpd, lmean, lm2, pit [rows] (None where not formed),
+        draws: the pooled count, info: PPD_INFO)."""
+        fn = getattr(self._lib, self._pfx + "predict_ppd", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_ppd")
+
+        def draws(smp):
+            probe = PpdOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if pr.ndim != 1:
+            raise ValueError(f"probs must be a vector, not shape {pr.shape}")
+        peers = list(peers)
+        own = draws(self)
+        rows_in, keep, rows, _ = self._summary_in(own, x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, None, route,
+                                                   stage_nodes, 0)
+
+        def vector(a, n, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+            if a.shape != (n,):
+                raise ValueError(f"{what} must have shape ({n},), not {a.shape}")
+            return a
+
+        pdc, hold_d = _peer_tables(peers, draws, peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
+        pec, hold_e = _peer_tables(peers, draws, peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
+        psg, hold_s = _peer_tables(peers, draws, None if peer_sigma is None else [np.asarray(t, dtype=np.float64).reshape(-1, 1) for t in peer_sigma], 1, "peer_sigma")
+        handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
+        yy, sg, rs = vector(y, rows, "y"), vector(sigma, own, "sigma"), vector(row_scale, rows, "row_scale")
+        if pit is None:
+            pit = int(link) == 0
+        scored = yy is not None
+        res = dict(quantiles=np.zeros((len(pr), rows)), lpd=np.zeros(rows) if scored and lpd else None, lmean=np.zeros(rows) if scored and moments else None,
+                   lm2=np.zeros(rows) if scored and moments else None, pit=np.zeros(rows) if scored and pit else None)
+        spare = np.zeros(1)          # (what a count beyond the library's limits would fill: refused there, which needs a pointer to tell the call from a query)
+        arg = PpdIn(rows=rows_in, y=_dp(yy), sigma=_dp(sg), row_scale=_dp(rs), noise_key=int(noise_key) & 0xFFFFFFFFFFFFFFFF, n_probs=len(pr),
+                    probs=_dp(pr), n_peers=len(peers), peers=handles if peers else None, peer_dense_coef=pdc, peer_ell_coef=pec, peer_sigma=psg,
+                    scratch_bytes=int(scratch_bytes))
+        out = PpdOut(quantiles=_dp(res["quantiles"]) if res["quantiles"].size else (_dp(spare) if len(pr) else None), lpd=_dp(res["lpd"]),
+                     lmean=_dp(res["lmean"]), lm2=_dp(res["lm2"]), pit=_dp(res["pit"]))
+        if not len(pr) and not any(res[k] is not None for k in ("lpd", "lmean", "pit")):
+            out.quantiles = _dp(spare)          # (nothing asked for: the library says so)
+        self.ppd_info = dict(zip(PPD_INFO, [0] * 9))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        w = [int(v) for v in out.info]
+        self.ppd_info = dict(zip(PPD_INFO, w[:3] + [w[3] >> 32, w[3] & 0xFFFFFFFF] + w[4:]))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep, hold_d, hold_e, hold_s, spare, yy, sg, rs
+        return dict(res, draws=int(out.num_samples), info=dict(self.ppd_info))
 
     def profile_leapfrog(self, n_evals: int = 10) -> dict:
         """Per-leapfrog O(N) sums of the hmc_mode 1 path timed with HIP events (measurement hook of the HIP library)."""
@@ -1003,6 +1070,7 @@ class StoredSampler:
     partial_dependence = Sampler.partial_dependence
     predict_quantiles = Sampler.predict_quantiles
     predict_contrast = Sampler.predict_contrast
+    predict_ppd = Sampler.predict_ppd
     export_bart_state = Sampler.export_bart_state
     get_kept_trees = Sampler.get_kept_trees
     get_kept_trees_indexed = Sampler.get_kept_trees_indexed

@@ -1628,6 +1628,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 #include "dev_summary.inc"
 #include "dev_pd.inc"
 #include "dev_quantile.inc"
+#include "dev_ppd.inc"
 #include "dev_contrast.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
@@ -2738,6 +2739,8 @@ class DevHip {
   void predict_quantiles(const QuantileCall& c) { quantile_run(stream_, a_.P, c, launches_); }
   // s4b_predict_contrast (dev_contrast.inc), likewise
   void predict_contrast(const ContrastCall& c) { contrast_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_ppd (dev_ppd.inc), likewise
+  void predict_ppd(const PpdCall& c) { ppd_run(stream_, a_.P, c, launches_); }
 
   // ---- Stan inputs
   void stan_inputs(int mode, bool wantTrain, double* cX, double* cZ, double* s0, double* trainOut) {

@@ -87,19 +87,10 @@ __global__ __launch_bounds__(PS_BLOCK) void k_predict_values(QuantileDev a) {
 __device__ __forceinline__ uint64_t qt_key(double x) { const uint64_t b = (uint64_t)__double_as_longlong(x); return (b >> 63) ? ~b : b | 0x8000000000000000ull; }
 __device__ __forceinline__ double qt_value(uint64_t k) { return __longlong_as_double((long long)((k >> 63) ? k & 0x7fffffffffffffffull : ~k)); }
 
-__global__ __launch_bounds__(QT_BLOCK) void k_row_quantiles(QuantileDev a) {
-  extern __shared__ __align__(16) unsigned char qs_lds[];
-  uint64_t* key = (uint64_t*)qs_lds;                                               // [R][Sp]
-  const int tid = threadIdx.x, Sp = a.Sp, R = a.R, N = R * Sp;
-  const int shift = 31 - __clz(Sp);                                                // Sp = 1 << shift
-  const int64_t S = a.S, row0 = (int64_t)blockIdx.x * R;                           // first row of the workgroup inside the chunk
-  for (int e = tid; e < N; e += QT_BLOCK) {
-    const int r = e >> shift, j = e & (Sp - 1);
-    key[e] = (j < S && row0 + r < a.chunkRows) ? qt_key(a.vals[(size_t)(row0 + r) * (size_t)S + (size_t)j]) : ~0ull;
-  }
-  __syncthreads();
-  // one bitonic network over all N elements, stopped at merge size Sp: ascending where bit `size` of the index INSIDE the segment is clear, which at
-  // size = Sp is everywhere
+// one bitonic network over all N = R * Sp keys of a sort workgroup, stopped at merge size Sp: ascending where bit `size` of the index INSIDE the segment
+// is clear, which at size = Sp is everywhere.  Every segment of Sp keys comes out ascending on its own.  Called by all QT_BLOCK threads, behind a barrier.
+__device__ __forceinline__ void qt_sort_rows(uint64_t* key, int N, int Sp) {
+  const int tid = threadIdx.x;
   for (int size = 2; size <= Sp; size <<= 1) {
     for (int j = size >> 1; j > 0; j >>= 1) {
       for (int pr = tid; pr < (N >> 1); pr += QT_BLOCK) {
@@ -111,7 +102,12 @@ __global__ __launch_bounds__(QT_BLOCK) void k_row_quantiles(QuantileDev a) {
       __syncthreads();
     }
   }
-  for (int e = tid; e < R * a.Q; e += QT_BLOCK) {
+}
+// R's type 7 of the sorted rows of a sort workgroup, stored prob-major: quantiles[j * nT + i]
+__device__ __forceinline__ void qt_type7_rows(const QuantileDev& a, const uint64_t* key, int64_t row0) {
+  const int R = a.R, Sp = a.Sp;
+  const int64_t S = a.S;
+  for (int e = threadIdx.x; e < R * a.Q; e += QT_BLOCK) {
     const int r = e % R, j = e / R;                                                // consecutive threads: consecutive rows of one prob
     if (row0 + r >= a.chunkRows) continue;
     const double h = a.probs[j] * (double)(S - 1);
@@ -120,6 +116,21 @@ __global__ __launch_bounds__(QT_BLOCK) void k_row_quantiles(QuantileDev a) {
     const double xl = qt_value(key[(size_t)r * Sp + lo]), xh = qt_value(key[(size_t)r * Sp + hi]);
     a.quantiles[(size_t)j * (size_t)a.nT + (size_t)(a.chunk0 + row0 + r)] = g == 0.0 ? xl : xl + g * (xh - xl);
   }
+}
+
+__global__ __launch_bounds__(QT_BLOCK) void k_row_quantiles(QuantileDev a) {
+  extern __shared__ __align__(16) unsigned char qs_lds[];
+  uint64_t* key = (uint64_t*)qs_lds;                                               // [R][Sp]
+  const int tid = threadIdx.x, Sp = a.Sp, R = a.R, N = R * Sp;
+  const int shift = 31 - __clz(Sp);                                                // Sp = 1 << shift
+  const int64_t S = a.S, row0 = (int64_t)blockIdx.x * R;                           // first row of the workgroup inside the chunk
+  for (int e = tid; e < N; e += QT_BLOCK) {
+    const int r = e >> shift, j = e & (Sp - 1);
+    key[e] = (j < S && row0 + r < a.chunkRows) ? qt_key(a.vals[(size_t)(row0 + r) * (size_t)S + (size_t)j]) : ~0ull;
+  }
+  __syncthreads();
+  qt_sort_rows(key, N, Sp);
+  qt_type7_rows(a, key, row0);
 }
 
 // uploads, two launches per chunk of rows, the download — on `stream`, everything allocated here freed here (summary_run's discipline)

@@ -82,6 +82,19 @@ S4B_PHX bool philox_trunc_normal(uint32_t k0, uint32_t k1, uint64_t draw, uint32
   return false;
 }
 
+// The standard normal deviate of element (row, draw) of a posterior predictive read-out (s4b_predict_ppd): the cosine deviate of
+// Box-Muller from the two uniforms of ONE block, counter = {row low, row high, draw, PPD_TAG}.  A pure function of (key, row, draw).  The last
+// counter word of the latents above is an attempt number below TN_MAX_ATTEMPTS; PPD_TAG lies above it ("PPD1"), so no block is shared with them
+// even under the same key.  The sine deviate of the block is not used.
+constexpr uint32_t PPD_TAG = 0x50504431u;
+static_assert(PPD_TAG >= (uint32_t)TN_MAX_ATTEMPTS, "the tag must differ from every attempt number of philox_trunc_normal");
+S4B_PHX double philox_normal(uint32_t k0, uint32_t k1, uint64_t row, uint32_t draw) {
+  const Philox4 c = {{(uint32_t)row, (uint32_t)(row >> 32), draw, PPD_TAG}};
+  const Philox4 r = philox4x32_10(c, k0, k1);
+  const double u1 = philox_u53(r.v[0], r.v[1]), u2 = philox_u53(r.v[2], r.v[3]);
+  return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
 }  // namespace s4b
 
 #endif

@@ -112,6 +112,20 @@ struct ContrastCall {
   int Q; const double* probs; int64_t scratchBytes; double* quantiles;          // as QuantileCall
 };
 
+// does the device layer form the posterior predictive read-out over the pooled kept draws (s4b_predict_ppd)?  As has_predict_quantiles.
+template <class D, class = void> struct has_predict_ppd : std::false_type {};
+template <class D> struct has_predict_ppd<D, std::void_t<decltype(&D::predict_ppd)>> : std::true_type {};
+// one s4b_predict_ppd call as the device layer sees it: the rows as a SummaryCall over the POOLED draws (as QuantileCall.rows; link: the response, 0
+// continuous, 1 binary — the value kernel writes z under either), sigma per POOLED draw (link 0), the validated arguments, each output NULL where
+// it was not asked for (lmean and lm2 together)
+struct PpdCall {
+  SummaryCall rows;
+  const double* y; const double* sigma; const double* rowScale;          // [nT] or NULL; [S] or NULL (link 1); [nT] or NULL
+  uint64_t noiseKey;
+  int Q; const double* probs; int64_t scratchBytes; double* quantiles;          // as QuantileCall; Q may be 0
+  double* lpd; double* lmean; double* lm2; double* pit;                  // [nT] each
+};
+
 template <class Dev>
 class SamplerCore {
  public:
@@ -750,6 +764,79 @@ class SamplerCore {
       return S;
     } else throw std::invalid_argument("predict_contrast: this device layer has no contrast kernels (the contrasts are formed by the HIP library only)");
   }
+  // s4b_predict_ppd: the posterior predictive distribution of new observations at the rows — type-7 quantiles of y_rep = z + sigma row_scale e — and the
+  // scores of held-out responses y (log predictive density, mean and squared deviations of the pointwise log-likelihood, PIT), per row over the
+  // pooled draws.  Pooled like predict_quantiles.  Everything is validated here, before any launch.
+  int64_t predict_ppd(const s4b_ppd_in* in, s4b_ppd_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_ppd: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in || (!out->quantiles && !out->lpd && !out->lmean && !out->lm2 && !out->pit)) return own;          // query
+    if constexpr (has_predict_ppd<Dev>::value) {
+      const std::string who = "predict_ppd";
+      const s4b_summary_in* rw = &in->rows;
+      if (rw->n_weights != 0) throw std::invalid_argument(who + ": n_weights must be 0 (every output is per row), not " + std::to_string(rw->n_weights));
+      check_summary_rows(rw, who, 0);
+      if (in->n_probs < 0 || in->n_probs > 16) throw std::invalid_argument(who + ": between 0 and 16 probs per call, not " + std::to_string(in->n_probs));
+      if (in->n_probs > 0 && rw->link != 0)
+        throw std::invalid_argument(who + ": n_probs > 0 under link 1: no y_rep is formed for a binary response, a row's predictive distribution is Bernoulli(mean of ev), which predict_summary gives");
+      if (in->n_probs > 0 && !in->probs) throw std::invalid_argument(who + ": NULL probs");
+      for (int j = 0; j < in->n_probs; ++j)
+        if (!(in->probs[j] >= 0.0 && in->probs[j] <= 1.0)) throw std::invalid_argument(who + ": prob " + std::to_string(in->probs[j]) + " outside [0, 1]");
+      if (in->n_probs > 0 && !out->quantiles) throw std::invalid_argument(who + ": n_probs > 0 needs quantiles");
+      if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
+      if ((out->lmean == nullptr) != (out->lm2 == nullptr)) throw std::invalid_argument(who + ": lmean and lm2 are given together or not at all");
+      const bool scores = out->lpd || out->lmean || out->pit;
+      if (scores && !in->y) throw std::invalid_argument(who + ": lpd, lmean, lm2 and pit need y");
+      if (out->pit && rw->link != 0) throw std::invalid_argument(who + ": pit must be NULL under link 1 (the PIT of a binary response is not formed)");
+      if (in->n_probs == 0 && !(in->y && scores)) throw std::invalid_argument(who + ": nothing asked for (no probs, no y with a score output)");
+      const int64_t nT = rw->n_test;
+      const int np = in->n_peers;
+      const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
+      // sigma per pooled draw, the row scale, the responses
+      std::vector<double> sigma;
+      if (rw->link == 0) {
+        if (!in->sigma) throw std::invalid_argument(who + ": link 0 needs sigma, one value per draw of the sampler");
+        if (np > 0 && !in->peer_sigma) throw std::invalid_argument(who + ": link 0 needs peer_sigma, one vector per peer");
+        sigma.reserve((size_t)S);
+        for (int x = -1; x < np; ++x) {
+          const double* sg = x < 0 ? in->sigma : in->peer_sigma[x];
+          const std::string whose = x < 0 ? std::string("sigma") : "peer_sigma[" + std::to_string(x) + "]";
+          if (!sg) throw std::invalid_argument(who + ": peer " + std::to_string(x) + ": link 0 needs its sigma vector");
+          const int64_t ps = x < 0 ? own : (int64_t)peers[x]->keptScale_.size() / 2;
+          for (int64_t k = 0; k < ps; ++k) {
+            if (!(std::isfinite(sg[k]) && sg[k] > 0.0)) throw std::invalid_argument(who + ": " + whose + " holds " + std::to_string(sg[k]) + " at draw " + std::to_string(k) + " (every sigma must be finite and > 0)");
+            sigma.push_back(sg[k]);
+          }
+        }
+        if (in->row_scale)
+          for (int64_t i = 0; i < nT; ++i) {
+            const double v = in->row_scale[i];
+            if (!(std::isfinite(v) && v >= 0.0)) throw std::invalid_argument(who + ": row_scale holds " + std::to_string(v) + " at row " + std::to_string(i) + " (finite and >= 0)");
+            if (in->y && v == 0.0) throw std::invalid_argument(who + ": row_scale is 0 at row " + std::to_string(i) + ": with y every row_scale must be > 0");
+          }
+      }
+      if (in->y)
+        for (int64_t i = 0; i < nT; ++i) {
+          const double v = in->y[i];
+          if (!std::isfinite(v)) throw std::invalid_argument(who + ": y holds " + std::to_string(v) + " at row " + std::to_string(i) + " (every y must be finite)");
+          if (rw->link != 0 && v != 0.0 && v != 1.0) throw std::invalid_argument(who + ": y holds " + std::to_string(v) + " at row " + std::to_string(i) + ": under link 1 every y is 0 or 1");
+        }
+      std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
+      bin_matrix(rw->x_test, (size_t)nT, xb);
+      PpdCall c{};
+      c.rows = summary_call(rw, xb, own); c.rows.info = out->info; c.rows.G = 0; c.rows.weights = nullptr;
+      c.y = in->y; c.sigma = rw->link == 0 ? sigma.data() : nullptr; c.rowScale = rw->link == 0 ? in->row_scale : nullptr; c.noiseKey = in->noise_key;
+      c.Q = in->n_probs; c.probs = in->probs; c.scratchBytes = in->scratch_bytes; c.quantiles = in->n_probs > 0 ? out->quantiles : nullptr;
+      c.lpd = out->lpd; c.lmean = out->lmean; c.lm2 = out->lm2; c.pit = out->pit;
+      DrawPool pool;
+      pool_concat(c.rows, pool, rw, xb, np, peers, in->peer_dense_coef, in->peer_ell_coef, S);
+      dev_.predict_ppd(c);
+      out->num_samples = S;
+      return S;
+    } else throw std::invalid_argument("predict_ppd: this device layer has no posterior predictive kernels (the read-out is formed by the HIP library only)");
+  }
   // ---- sampler state as a byte string (layout: include/stan4bart_amd.h, s4b_get_state)
   int64_t get_state(void* buf, int64_t cap) {
     live();
@@ -1102,7 +1189,7 @@ class SamplerCore {
       for (int c = 0; c < m; ++c) cuts_[(size_t)j][(size_t)c] = mn + (double)(c + 1) * (mx - mn) / (double)(m + 1);
     }
   }
-  // ---- pooling of several samplers' kept draws into one call (s4b_predict_quantiles, s4b_predict_contrast)
+  // ---- pooling of several samplers' kept draws into one call (s4b_predict_quantiles, s4b_predict_contrast, s4b_predict_ppd)
   // the peer rules, checked before anything is launched: returns the pooled draw count S (this sampler's draws, then the peers')
   int64_t pool_check(const std::string& who, const s4b_summary_in* rw, int np, bool havePeers, const SamplerCore* const* peers, const double* const* peerDenseCoef,
                      const double* const* peerEllCoef) const {

@@ -607,6 +607,67 @@ class Stan4bartFit:
             average = average.reshape(w.shape[0], len(self.samplers), -1).transpose(0, 2, 1)
         return {"mean": r["mean"], "sd": sd, "average": average, "probs": pr, "quantiles": r["quantiles"], "draws": n}
 
+    # ------------------------------------------------------------------ predict_ppd
+    def predict_ppd(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, y=None, probs=(0.025, 0.5, 0.975),
+                    obs_weights=None, sample_new_levels: bool = True, seed: Optional[int] = None):
+        """The posterior predictive distribution at new rows, read out on the device without ``predict(type="ppd")``'s [rows x draws] matrix, in ONE
+        pooled call (``s4b_predict_ppd``: the first chain's sampler with the others as its peers).  Continuous response: ``quantiles`` [Q, rows],
+        the ``probs`` quantiles (R's type 7) of ``y_rep = ev + sigma sqrt(1 / obs_weights) e`` — prediction intervals for new observations —
+        with sigma each chain's ``aux.1`` draws and ``e`` a counter-based standard normal, a pure function of (``noise_key``, row, pooled draw).
+        ``noise_key`` comes from ``seed`` (None: fresh entropy) and is returned, with the ``seed`` that reproduces the whole call.  Binary response:
+        no replicate is formed (a row's predictive distribution is Bernoulli(mean of ev): ``predict_summary``); ``probs`` must be empty.
+        With held-out responses ``y`` [rows] the call scores them per row: ``lpd`` (log mean_k p(y | theta_k)), ``p_waic`` (var_k log p, ddof 1),
+        ``elpd_waic = lpd - p_waic``, ``pit`` (continuous only), and over the rows ``elpd_waic_total``, its ``se = sqrt(rows var(elpd_waic))``
+        (ddof 1) and, with two or more probs, ``coverage``: the share of ``y`` inside the outermost pair of requested quantiles.
+        Needs bart_args keepTrees."""
+        if not self.samplers:
+            raise ValueError("predict_ppd requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_ppd needs x_bart, the new rows of the BART predictors")
+        binary = self.family == "binomial"
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or len(pr) > 16 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of at most 16 values in [0, 1], not {probs!r}")
+        if binary and len(pr):
+            raise ValueError("predict_ppd forms no quantiles for a binary response: a row's predictive distribution is Bernoulli(mean of ev), which "
+                             "predict_summary gives (pass probs=())")
+        if not len(pr) and y is None:
+            raise ValueError("predict_ppd: nothing asked for (no probs, no y)")
+        x_bart = np.asarray(x_bart, dtype=np.float64)
+        rows = x_bart.shape[0]
+        if y is not None:
+            y = np.asarray(y, dtype=np.float64)
+            if y.shape != (rows,):
+                raise ValueError(f"y must have shape [{rows}], not {y.shape}")
+        row_scale = None
+        if obs_weights is not None:
+            w = np.asarray(obs_weights, dtype=np.float64)
+            if w.shape != (rows,) or not np.all(np.isfinite(w) & (w > 0.0)):
+                raise ValueError(f"obs_weights must be {rows} finite values > 0")
+            row_scale = 1.0 / np.sqrt(w)                             # reference R/generics.R:452-459: sd = sigma sqrt(1 / w)
+        ss = np.random.SeedSequence(seed)                            # (default_rng(seed) is default_rng(SeedSequence(seed)): predict's draws of unseen levels)
+        noise_key = int(ss.generate_state(1, np.uint64)[0])
+        linear = self._summary_linear("ev", X, groups, offset, sample_new_levels, np.random.default_rng(ss))
+        first, others = linear(0), [linear(c) for c in range(1, len(self.samplers))]
+        sig = self.stan[self.par_names.index("aux.1")]               # [iter, chain]
+        r = self.samplers[0].predict_ppd(x_bart, pr, y=y, sigma=None if binary else sig[:, 0], row_scale=row_scale, noise_key=noise_key,
+                                         peers=self.samplers[1:], peer_sigma=None if binary else [sig[:, c] for c in range(1, len(self.samplers))],
+                                         peer_dense_coef=None if first["dense"] is None else [a["dense_coef"] for a in others],
+                                         peer_ell_coef=None if first["ell_index"] is None else [a["ell_coef"] for a in others], **first)
+        S = r["draws"]
+        out = {"probs": pr, "quantiles": r["quantiles"], "draws": S, "noise_key": noise_key, "seed": ss.entropy}
+        if y is not None:
+            p_waic = r["lm2"] / (S - 1) if S > 1 else np.full(rows, np.nan)
+            elpd = r["lpd"] - p_waic
+            out.update(lpd=r["lpd"], p_waic=p_waic, elpd_waic=elpd, elpd_waic_total=float(elpd.sum()),
+                       se=float(np.sqrt(rows * np.var(elpd, ddof=1))) if rows > 1 else float("nan"))
+            if not binary:
+                out["pit"] = r["pit"]
+            if len(pr) >= 2:
+                lo, hi = r["quantiles"][int(np.argmin(pr))], r["quantiles"][int(np.argmax(pr))]
+                out["coverage"] = float(np.mean((y >= lo) & (y <= hi)))
+        return out
+
     def export_bart_states(self) -> list:
         """``stan4bart_exportBARTState`` per chain (reference R/stan4bart_fit.R:572-580): byte strings that
         ``attach_stored_samplers`` turns back into predict-capable samplers, in this or another process."""
