@@ -436,6 +436,58 @@ typedef struct {
 } s4b_ppd_out;
 int S4B_FN(predict_ppd)(s4b_sampler* s, const s4b_ppd_in* in, s4b_ppd_out* out);
 
+/* extension (R: loo::loo() on the rows-times-draws log-likelihood matrix, formed on the device): PSIS-LOO, Pareto-smoothed importance-sampling
+ * leave-one-out, per row over the draws of `s` and its peers, pooled as predict_quantiles pools them (the draws of `s`, then the peers' in their order,
+ * S in all, S <= 16384).  It follows loo's do_psis_i / psis_smooth_tail / gpdfit (Vehtari, Simpson, Gelman, Yao, Gabry; the fit: Zhang & Stephens
+ * 2009), restated here from the published algorithm; it is NOT pinned against the R package (no R in the test environment), only against the numpy
+ * model of tests/loo_cases.py.  l(i,k) is exactly predict_ppd's log-likelihood of y_i under pooled draw k, link 0 or 1: the same
+ * sd = sigma[k] row_scale[i], the same log Phi at the signed argument.  lr_k = -l(i,k) is the log importance ratio; lr(0) <= ... <= lr(S-1) the
+ * sorted row, mx = lr(S-1), lw(j) = lr(j) - mx.
+ *   1  tail length M = tail_len; tail_len = 0: min(ceil(S / 5), ceil(3 sqrt S)) — loo's ceiling(min(0.2 S, 3 sqrt(S / r_eff))) at r_eff = 1 —,
+ *      ceil(3 sqrt S) being the smallest m with m m >= 9 S, formed in integers on the host.  A given tail_len must lie in [5, min(S - 1, 1024)].
+ *   2  no smoothing where M < 5 (every pool below 21 draws under the default) or lw(S-1) - lw(S-M) < 2^-52 / 100: khat = +inf, raw weights (loo's choice).
+ *   3  else the generalised-Pareto fit: ec = exp(lw(S-M-1)); x_j = exp(lw(S-M+j)) - ec, j = 0 .. M-1 ascending; N = M; G = 30 + floor(sqrt N);
+ *      xs = x[floor(N / 4 + 0.5) - 1]; theta_g = 1 / x_{N-1} + (1 - sqrt(G / (g - 0.5))) / (3 xs), g = 1 .. G; kappa_g = mean_j log1p(-theta_g x_j);
+ *      L_g = N (log(-theta_g / kappa_g) - kappa_g - 1); w_g = exp(L_g - max L) / sum exp(L - max L); theta^ = sum theta_g w_g;
+ *      k0 = mean_j log1p(-theta^ x_j); sigma = -k0 / theta^; khat = k0 N / (N + 10) + 5 / (N + 10).  khat or sigma not finite: khat = +inf, no
+ *      smoothing.  Else, p_j = (j + 0.5) / N:  lw'(S-M+j) = min(0, log(sigma expm1(-khat log1p(-p_j)) / khat + ec)).
+ *   4  outputs per row, lw' the smoothed weights on the tail and lw elsewhere; n_test doubles each, each may be NULL, at least one is wanted:
+ *        elpd_loo[i]   log sum_j exp(lw'(j) - lr(j)) - log sum_j exp(lw'(j)), both log-sum-exps with the maximum taken out
+ *        pareto_k[i]   khat
+ *        lpd[i]        log sum_j exp(-lr(j)) - log S: predict_ppd's lpd, summed here in SORTED order — it agrees within its bound, not bit for bit
+ *        ess[i]        (sum_j e^{lw'(j)})^2 / sum_j e^{2 lw'(j)}
+ * The smoothed weight belongs to the RANK of its draw, and outside the tail lw + l = -mx whichever draw it is: the sorted row alone determines every
+ * output, ties included.  `rows`, y (required), sigma, row_scale, the peers with peer_sigma, scratch_bytes, the chunking and the query
+ * form (all outputs NULL or in = NULL: num_samples of `s` alone) are predict_ppd's; there is no noise key and there are no probs.  Everything is
+ * checked before anything is launched; a refused call leaves info all zero.  Two calls return the same bits, on both routes, with live or stored
+ * samplers, under any chunking.  Device memory: DESIGN.md 5.10. */
+typedef struct {
+  s4b_summary_in rows;            /* n_weights 0; link: the response, 0 continuous, 1 binary */
+  const double* y;                /* n_test responses */
+  const double* sigma;            /* one per draw of `s` (link 0) */
+  const double* row_scale;        /* n_test, or NULL: 1 */
+  int32_t tail_len;               /* 0: the default; else 5 .. min(S - 1, 1024) */
+  int32_t n_peers;
+  s4b_sampler* const* peers;
+  const double* const* peer_dense_coef;
+  const double* const* peer_ell_coef;
+  const double* const* peer_sigma;        /* [n_peers] vectors (one value per draw of that peer), link 0 */
+  int64_t scratch_bytes;
+} s4b_loo_in;
+typedef struct {
+  double* elpd_loo;               /* n_test each, or NULL */
+  double* pareto_k;
+  double* lpd;
+  double* ess;
+  int64_t num_samples;            /* pooled draws S */
+  int32_t tail_len;               /* the M the call used (0 after a query or a refusal) */
+  /* what the call did, s4b_quantile_out.info's layout: [0] route of the value kernel (1 LDS-staged, 2 global; 0: nothing was launched), [1] rows per
+   * chunk C, [2] chunks, [3] (rows per workgroup of k_loo_rows) << 32 | draws padded to a power of two, [4] nodes of the largest pooled draw,
+   * [5] kernel launches (2 per chunk), [6] bytes of device memory the call allocated, [7] pooled draws */
+  int64_t info[8];
+} s4b_loo_out;
+int S4B_FN(predict_loo)(s4b_sampler* s, const s4b_loo_in* in, s4b_loo_out* out);
+
 /* The state of a chain BETWEEN TWO GIBBS ITERATIONS as one relocatable byte string: what the next iteration starts from.  It is
  * the hook of the teacher-forced parity tests (state of one implementation injected into the other before every compared
  * transition) and lets a chain continue in another sampler created from the same data; it is not an archive of a fit: the

@@ -135,12 +135,25 @@ class PpdOut(C.Structure):             # s4b_ppd_out
                 ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
 
 
+class LooIn(C.Structure):              # s4b_loo_in
+    _fields_ = [("rows", SummaryIn), ("y", c_double_p), ("sigma", c_double_p), ("row_scale", c_double_p), ("tail_len", C.c_int32),
+                ("n_peers", C.c_int32), ("peers", C.POINTER(C.c_void_p)), ("peer_dense_coef", C.POINTER(c_double_p)),
+                ("peer_ell_coef", C.POINTER(c_double_p)), ("peer_sigma", C.POINTER(c_double_p)), ("scratch_bytes", C.c_int64)]
+
+
+class LooOut(C.Structure):             # s4b_loo_out
+    _fields_ = [("elpd_loo", c_double_p), ("pareto_k", c_double_p), ("lpd", c_double_p), ("ess", c_double_p), ("num_samples", C.c_int64),
+                ("tail_len", C.c_int32), ("info", C.c_int64 * 8)]
+
+
 SUMMARY_ROUTES = {"auto": 0, "staged": 1, "global": 2}
 SUMMARY_INFO = ("route", "rows_per_tile", "workgroups", "staging_bytes", "largest_draw_nodes", "launches", "device_bytes", "staging_nodes")
 PD_INFO = SUMMARY_INFO[:7] + ("largest_affected", "total_affected")          # (the last two share info[7]: trees with a rule on a varied predictor)
 QUANTILE_INFO = ("route", "rows_per_chunk", "chunks", "rows_per_sort", "padded_draws", "largest_draw_nodes", "launches", "device_bytes", "draws")
 CONTRAST_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "differing_columns", "largest_affected", "total_affected")
 PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
+LOO_INFO = QUANTILE_INFO               # (s4b_loo_out.info likewise; rows_per_sort: rows per workgroup of k_loo_rows)
+LOO_OUTPUTS = ("elpd_loo", "pareto_k", "lpd", "ess")
 PD_GRID_MAX = 64                       # grid points per s4b_partial_dependence call
 
 
@@ -385,6 +398,7 @@ class Sampler:
             "predict_quantiles": [vp, C.POINTER(QuantileIn), C.POINTER(QuantileOut)],
             "predict_contrast": [vp, C.POINTER(ContrastIn), C.POINTER(ContrastOut)],
             "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
+            "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
             "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
         }
         for name, argtypes in sig.items():
@@ -950,6 +964,57 @@ class Sampler:
         del keep, hold_d, hold_e, hold_s, spare, yy, sg, rs
         return dict(res, draws=int(out.num_samples), info=dict(self.ppd_info))
 
+    def predict_loo(self, x_test: np.ndarray, y=None, sigma=None, row_scale=None, tail_len: int = 0, peers=(), peer_sigma=None, peer_dense_coef=None,
+                    peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None, ell_coef=None, link: int = 0,
+                    outputs=LOO_OUTPUTS, route="auto", stage_nodes: int = 0, scratch_bytes: int = 0) -> dict:
+        """``s4b_predict_loo``: PSIS-LOO of the responses ``y`` [rows] per row over the kept draws of this sampler and of ``peers``, pooled in ONE
+        device call as ``predict_ppd`` pools them, with its ``link``, ``sigma`` / ``peer_sigma`` and ``row_scale``.  ``tail_len`` 0: the default
+        min(ceil(S / 5), ceil(3 sqrt S)); else 5 .. min(S - 1, 1024).  ``outputs``: which of LOO_OUTPUTS are formed.  Returns dict(elpd_loo,
+        pareto_k (+inf where no tail was fitted), lpd, ess [rows] (None where not asked for), draws: the pooled count, tail_len: the one used,
+        info: LOO_INFO)."""
+        fn = getattr(self._lib, self._pfx + "predict_loo", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_loo")
+
+        def draws(smp):
+            probe = LooOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        outputs = tuple(outputs)
+        self.loo_info = dict(zip(LOO_INFO, [0] * 9))
+        if not outputs or not set(outputs) <= set(LOO_OUTPUTS):          # (no output pointer at all is the library's query form: refused here)
+            raise ValueError(f"outputs must name at least one of {LOO_OUTPUTS}, not {outputs!r}")
+        peers = list(peers)
+        own = draws(self)
+        rows_in, keep, rows, _ = self._summary_in(own, x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, None, route,
+                                                   stage_nodes, 0)
+
+        def vector(a, n, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+            if a.shape != (n,):
+                raise ValueError(f"{what} must have shape ({n},), not {a.shape}")
+            return a
+
+        pdc, hold_d = _peer_tables(peers, draws, peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
+        pec, hold_e = _peer_tables(peers, draws, peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
+        psg, hold_s = _peer_tables(peers, draws, None if peer_sigma is None else [np.asarray(t, dtype=np.float64).reshape(-1, 1) for t in peer_sigma], 1, "peer_sigma")
+        handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
+        yy, sg, rs = vector(y, rows, "y"), vector(sigma, own, "sigma"), vector(row_scale, rows, "row_scale")
+        res = {k: (np.zeros(rows) if k in outputs else None) for k in LOO_OUTPUTS}
+        spare = np.zeros(1)          # (no rows: what the library needs to tell the call from a query)
+        arg = LooIn(rows=rows_in, y=_dp(yy), sigma=_dp(sg), row_scale=_dp(rs), tail_len=int(tail_len), n_peers=len(peers), peers=handles if peers else None,
+                    peer_dense_coef=pdc, peer_ell_coef=pec, peer_sigma=psg, scratch_bytes=int(scratch_bytes))
+        out = LooOut(**{k: _dp(v if v.size else spare) for k, v in res.items() if v is not None})
+        self.loo_info = dict(zip(LOO_INFO, [0] * 9))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        w = [int(v) for v in out.info]
+        self.loo_info = dict(zip(LOO_INFO, w[:3] + [w[3] >> 32, w[3] & 0xFFFFFFFF] + w[4:]))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep, hold_d, hold_e, hold_s, spare, yy, sg, rs
+        return dict(res, draws=int(out.num_samples), tail_len=int(out.tail_len), info=dict(self.loo_info))
+
     def profile_leapfrog(self, n_evals: int = 10) -> dict:
         """Per-leapfrog O(N) sums of the hmc_mode 1 path timed with HIP events (measurement hook of the HIP library)."""
         out = (C.c_double * 8)()
@@ -1071,6 +1136,7 @@ class StoredSampler:
     predict_quantiles = Sampler.predict_quantiles
     predict_contrast = Sampler.predict_contrast
     predict_ppd = Sampler.predict_ppd
+    predict_loo = Sampler.predict_loo
     export_bart_state = Sampler.export_bart_state
     get_kept_trees = Sampler.get_kept_trees
     get_kept_trees_indexed = Sampler.get_kept_trees_indexed

@@ -1629,6 +1629,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 #include "dev_pd.inc"
 #include "dev_quantile.inc"
 #include "dev_ppd.inc"
+#include "dev_loo.inc"
 #include "dev_contrast.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
@@ -2741,6 +2742,8 @@ class DevHip {
   void predict_contrast(const ContrastCall& c) { contrast_run(stream_, a_.P, c, launches_); }
   // s4b_predict_ppd (dev_ppd.inc), likewise
   void predict_ppd(const PpdCall& c) { ppd_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_loo (dev_loo.inc), likewise
+  void predict_loo(const LooCall& c) { loo_run(stream_, a_.P, c, launches_); }
 
   // ---- Stan inputs
   void stan_inputs(int mode, bool wantTrain, double* cX, double* cZ, double* s0, double* trainOut) {

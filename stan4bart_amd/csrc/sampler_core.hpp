@@ -126,6 +126,19 @@ struct PpdCall {
   double* lpd; double* lmean; double* lm2; double* pit;                  // [nT] each
 };
 
+// does the device layer form the PSIS-LOO read-out over the pooled kept draws (s4b_predict_loo)?  As has_predict_ppd.
+template <class D, class = void> struct has_predict_loo : std::false_type {};
+template <class D> struct has_predict_loo<D, std::void_t<decltype(&D::predict_loo)>> : std::true_type {};
+// one s4b_predict_loo call as the device layer sees it: the rows as PpdCall.rows (link: the response), sigma per POOLED draw (link 0), the tail
+// length M resolved (the default formed, a given one checked against the pool), each output NULL where it was not asked for
+struct LooCall {
+  SummaryCall rows;
+  const double* y; const double* sigma; const double* rowScale;          // [nT]; [S] or NULL (link 1); [nT] or NULL
+  int tailLen;                                                           // M: below 5 no tail is fitted
+  int64_t scratchBytes;
+  double* elpd; double* khat; double* lpd; double* ess;                  // [nT] each
+};
+
 template <class Dev>
 class SamplerCore {
  public:
@@ -796,33 +809,7 @@ class SamplerCore {
       const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
       // sigma per pooled draw, the row scale, the responses
       std::vector<double> sigma;
-      if (rw->link == 0) {
-        if (!in->sigma) throw std::invalid_argument(who + ": link 0 needs sigma, one value per draw of the sampler");
-        if (np > 0 && !in->peer_sigma) throw std::invalid_argument(who + ": link 0 needs peer_sigma, one vector per peer");
-        sigma.reserve((size_t)S);
-        for (int x = -1; x < np; ++x) {
-          const double* sg = x < 0 ? in->sigma : in->peer_sigma[x];
-          const std::string whose = x < 0 ? std::string("sigma") : "peer_sigma[" + std::to_string(x) + "]";
-          if (!sg) throw std::invalid_argument(who + ": peer " + std::to_string(x) + ": link 0 needs its sigma vector");
-          const int64_t ps = x < 0 ? own : (int64_t)peers[x]->keptScale_.size() / 2;
-          for (int64_t k = 0; k < ps; ++k) {
-            if (!(std::isfinite(sg[k]) && sg[k] > 0.0)) throw std::invalid_argument(who + ": " + whose + " holds " + std::to_string(sg[k]) + " at draw " + std::to_string(k) + " (every sigma must be finite and > 0)");
-            sigma.push_back(sg[k]);
-          }
-        }
-        if (in->row_scale)
-          for (int64_t i = 0; i < nT; ++i) {
-            const double v = in->row_scale[i];
-            if (!(std::isfinite(v) && v >= 0.0)) throw std::invalid_argument(who + ": row_scale holds " + std::to_string(v) + " at row " + std::to_string(i) + " (finite and >= 0)");
-            if (in->y && v == 0.0) throw std::invalid_argument(who + ": row_scale is 0 at row " + std::to_string(i) + ": with y every row_scale must be > 0");
-          }
-      }
-      if (in->y)
-        for (int64_t i = 0; i < nT; ++i) {
-          const double v = in->y[i];
-          if (!std::isfinite(v)) throw std::invalid_argument(who + ": y holds " + std::to_string(v) + " at row " + std::to_string(i) + " (every y must be finite)");
-          if (rw->link != 0 && v != 0.0 && v != 1.0) throw std::invalid_argument(who + ": y holds " + std::to_string(v) + " at row " + std::to_string(i) + ": under link 1 every y is 0 or 1");
-        }
+      check_responses(who, rw, in->y, in->sigma, in->peer_sigma, in->row_scale, np, peers, S, sigma);
       std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
       bin_matrix(rw->x_test, (size_t)nT, xb);
       PpdCall c{};
@@ -836,6 +823,51 @@ class SamplerCore {
       out->num_samples = S;
       return S;
     } else throw std::invalid_argument("predict_ppd: this device layer has no posterior predictive kernels (the read-out is formed by the HIP library only)");
+  }
+  // the default tail length of PSIS over S pooled draws: min(ceil(S / 5), ceil(3 sqrt S)) — loo's ceiling(min(0.2 S, 3 sqrt(S / r_eff))) at r_eff = 1 —
+  // with ceil(3 sqrt S) the smallest m with m m >= 9 S, formed in integers
+  static int64_t loo_tail_len(int64_t S) {
+    int64_t m = (int64_t)std::floor(3.0 * std::sqrt((double)S));
+    while (m > 0 && (m - 1) * (m - 1) >= 9 * S) --m;
+    while (m * m < 9 * S) ++m;
+    return std::min((S + 4) / 5, m);
+  }
+  // s4b_predict_loo: PSIS-LOO of held-out (or the training) responses y per row over the pooled draws — elpd_loo, the Pareto shape khat of the
+  // importance ratios' tail, the lpd and the effective sample size of the smoothed weights.  Pooled and validated like predict_ppd, before any launch.
+  int64_t predict_loo(const s4b_loo_in* in, s4b_loo_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_loo: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own; out->tail_len = 0;
+    if (!in || (!out->elpd_loo && !out->pareto_k && !out->lpd && !out->ess)) return own;          // query
+    if constexpr (has_predict_loo<Dev>::value) {
+      const std::string who = "predict_loo";
+      const s4b_summary_in* rw = &in->rows;
+      if (rw->n_weights != 0) throw std::invalid_argument(who + ": n_weights must be 0 (every output is per row), not " + std::to_string(rw->n_weights));
+      check_summary_rows(rw, who, 0);
+      if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
+      if (!in->y) throw std::invalid_argument(who + ": NULL y (the importance ratios are those of the responses)");
+      const int64_t nT = rw->n_test;
+      const int np = in->n_peers;
+      const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
+      const int64_t most = std::min<int64_t>(S - 1, 1024);
+      if (in->tail_len != 0 && (in->tail_len < 5 || in->tail_len > most))
+        throw std::invalid_argument(who + ": tail_len " + std::to_string(in->tail_len) + " outside [5, " + std::to_string(most) + "] (0: the default; at most 1024 and the pooled draws - 1, " + std::to_string(S) + " here)");
+      std::vector<double> sigma;
+      check_responses(who, rw, in->y, in->sigma, in->peer_sigma, in->row_scale, np, peers, S, sigma);
+      std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
+      bin_matrix(rw->x_test, (size_t)nT, xb);
+      LooCall c{};
+      c.rows = summary_call(rw, xb, own); c.rows.info = out->info; c.rows.G = 0; c.rows.weights = nullptr;
+      c.y = in->y; c.sigma = rw->link == 0 ? sigma.data() : nullptr; c.rowScale = rw->link == 0 ? in->row_scale : nullptr;
+      c.tailLen = (int)(in->tail_len != 0 ? in->tail_len : loo_tail_len(S)); c.scratchBytes = in->scratch_bytes;
+      c.elpd = out->elpd_loo; c.khat = out->pareto_k; c.lpd = out->lpd; c.ess = out->ess;
+      DrawPool pool;
+      pool_concat(c.rows, pool, rw, xb, np, peers, in->peer_dense_coef, in->peer_ell_coef, S);
+      dev_.predict_loo(c);
+      out->num_samples = S; out->tail_len = c.tailLen;
+      return S;
+    } else throw std::invalid_argument("predict_loo: this device layer has no PSIS-LOO kernels (the read-out is formed by the HIP library only)");
   }
   // ---- sampler state as a byte string (layout: include/stan4bart_amd.h, s4b_get_state)
   int64_t get_state(void* buf, int64_t cap) {
@@ -1188,6 +1220,39 @@ class SamplerCore {
       cuts_[(size_t)j].resize((size_t)m);
       for (int c = 0; c < m; ++c) cuts_[(size_t)j][(size_t)c] = mn + (double)(c + 1) * (mx - mn) / (double)(m + 1);
     }
+  }
+  // the sigma / row_scale / y rules of s4b_predict_ppd and s4b_predict_loo: under link 0 one finite sigma > 0 per draw of the sampler and of every peer
+  // (gathered into `sigma` in pooled order) and a finite row_scale >= 0 (> 0 beside y); every y finite, under link 1 exactly 0 or 1
+  void check_responses(const std::string& who, const s4b_summary_in* rw, const double* y, const double* sigma0, const double* const* peerSigma,
+                       const double* rowScale, int np, const SamplerCore* const* peers, int64_t S, std::vector<double>& sigma) const {
+    const int64_t nT = rw->n_test, own = (int64_t)keptScale_.size() / 2;
+    if (rw->link == 0) {
+      if (!sigma0) throw std::invalid_argument(who + ": link 0 needs sigma, one value per draw of the sampler");
+      if (np > 0 && !peerSigma) throw std::invalid_argument(who + ": link 0 needs peer_sigma, one vector per peer");
+      sigma.reserve((size_t)S);
+      for (int x = -1; x < np; ++x) {
+        const double* sg = x < 0 ? sigma0 : peerSigma[x];
+        const std::string whose = x < 0 ? std::string("sigma") : "peer_sigma[" + std::to_string(x) + "]";
+        if (!sg) throw std::invalid_argument(who + ": peer " + std::to_string(x) + ": link 0 needs its sigma vector");
+        const int64_t ps = x < 0 ? own : (int64_t)peers[x]->keptScale_.size() / 2;
+        for (int64_t k = 0; k < ps; ++k) {
+          if (!(std::isfinite(sg[k]) && sg[k] > 0.0)) throw std::invalid_argument(who + ": " + whose + " holds " + std::to_string(sg[k]) + " at draw " + std::to_string(k) + " (every sigma must be finite and > 0)");
+          sigma.push_back(sg[k]);
+        }
+      }
+      if (rowScale)
+        for (int64_t i = 0; i < nT; ++i) {
+          const double v = rowScale[i];
+          if (!(std::isfinite(v) && v >= 0.0)) throw std::invalid_argument(who + ": row_scale holds " + std::to_string(v) + " at row " + std::to_string(i) + " (finite and >= 0)");
+          if (y && v == 0.0) throw std::invalid_argument(who + ": row_scale is 0 at row " + std::to_string(i) + ": with y every row_scale must be > 0");
+        }
+    }
+    if (y)
+      for (int64_t i = 0; i < nT; ++i) {
+        const double v = y[i];
+        if (!std::isfinite(v)) throw std::invalid_argument(who + ": y holds " + std::to_string(v) + " at row " + std::to_string(i) + " (every y must be finite)");
+        if (rw->link != 0 && v != 0.0 && v != 1.0) throw std::invalid_argument(who + ": y holds " + std::to_string(v) + " at row " + std::to_string(i) + ": under link 1 every y is 0 or 1");
+      }
   }
   // ---- pooling of several samplers' kept draws into one call (s4b_predict_quantiles, s4b_predict_contrast, s4b_predict_ppd)
   // the peer rules, checked before anything is launched: returns the pooled draw count S (this sampler's draws, then the peers')

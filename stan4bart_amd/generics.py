@@ -668,6 +668,59 @@ class Stan4bartFit:
                 out["coverage"] = float(np.mean((y >= lo) & (y <= hi)))
         return out
 
+    # ------------------------------------------------------------------ predict_loo
+    def predict_loo(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, y=None, obs_weights=None, r_eff: float = 1.0,
+                    sample_new_levels: bool = True, seed: Optional[int] = None):
+        """PSIS-LOO (``loo::loo()`` on the log-likelihood matrix) of the responses ``y`` [rows] at the rows, read out on the device without the
+        [rows x draws] matrix, in ONE pooled call (``s4b_predict_loo``: the first chain's sampler with the others as its peers).  The likelihood is
+        ``predict_ppd``'s: normal with sd = sigma sqrt(1 / obs_weights), or Bernoulli-probit.  A scalar ``r_eff`` in (0, 1] sets the tail length
+        ``ceil(min(S / 5, 3 sqrt(S / r_eff)))`` (at most 1024).  Per row: ``elpd_loo``, ``pareto_k`` (+inf where no tail was fitted), ``lpd``,
+        ``p_loo = lpd - elpd_loo``, ``ess``; over the rows ``elpd_loo_total``, ``p_loo_total``, ``se = sqrt(rows var(elpd_loo))`` (ddof 1),
+        ``k_threshold = min(1 - 1 / log10(S), 0.7)``, ``n_high_k`` (rows above it), ``draws`` and ``tail_len``.  Restated from the published
+        algorithm, not pinned against the R package.  Needs bart_args keepTrees."""
+        if not self.samplers:
+            raise ValueError("predict_loo requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_loo needs x_bart, the rows of the BART predictors")
+        if y is None:
+            raise ValueError("predict_loo needs y, the responses of the rows")
+        x_bart = np.asarray(x_bart, dtype=np.float64)
+        rows = x_bart.shape[0]
+        y = np.asarray(y, dtype=np.float64)
+        if y.shape != (rows,):
+            raise ValueError(f"y must have shape [{rows}], not {y.shape}")
+        if not (np.ndim(r_eff) == 0 and 0.0 < float(r_eff) <= 1.0):
+            raise ValueError(f"'r_eff' must be one value in (0, 1], not {r_eff!r}")
+        binary = self.family == "binomial"
+        row_scale = None
+        if obs_weights is not None:
+            w = np.asarray(obs_weights, dtype=np.float64)
+            if w.shape != (rows,) or not np.all(np.isfinite(w) & (w > 0.0)):
+                raise ValueError(f"obs_weights must be {rows} finite values > 0")
+            row_scale = 1.0 / np.sqrt(w)                             # reference R/generics.R:452-459: sd = sigma sqrt(1 / w)
+        sig = self.stan[self.par_names.index("aux.1")]               # [iter, chain]
+        S = sig.shape[0] * len(self.samplers)
+        tail_len = 0                                                 # r_eff = 1: the library's own integer rule
+        if float(r_eff) != 1.0:
+            tail_len = int(np.ceil(min(S / 5.0, 3.0 * np.sqrt(S / float(r_eff)))))
+            if tail_len > 1024:
+                raise ValueError(f"r_eff = {r_eff!r} asks for a tail of {tail_len} of the {S} draws: at most 1024")
+            if tail_len < 5:                                         # (20 draws or fewer: no tail is fitted under any r_eff, the default says the same)
+                tail_len = 0
+        linear = self._summary_linear("ev", X, groups, offset, sample_new_levels, np.random.default_rng(seed))
+        first, others = linear(0), [linear(c) for c in range(1, len(self.samplers))]
+        r = self.samplers[0].predict_loo(x_bart, y=y, sigma=None if binary else sig[:, 0], row_scale=row_scale, tail_len=tail_len,
+                                         peers=self.samplers[1:], peer_sigma=None if binary else [sig[:, c] for c in range(1, len(self.samplers))],
+                                         peer_dense_coef=None if first["dense"] is None else [a["dense_coef"] for a in others],
+                                         peer_ell_coef=None if first["ell_index"] is None else [a["ell_coef"] for a in others], **first)
+        S = r["draws"]
+        p_loo = r["lpd"] - r["elpd_loo"]
+        thr = min(1.0 - 1.0 / np.log10(S), 0.7) if S > 1 else float("-inf")
+        return {"elpd_loo": r["elpd_loo"], "pareto_k": r["pareto_k"], "lpd": r["lpd"], "p_loo": p_loo, "ess": r["ess"],
+                "elpd_loo_total": float(r["elpd_loo"].sum()), "p_loo_total": float(p_loo.sum()),
+                "se": float(np.sqrt(rows * np.var(r["elpd_loo"], ddof=1))) if rows > 1 else float("nan"),
+                "k_threshold": float(thr), "n_high_k": int(np.sum(r["pareto_k"] > thr)), "draws": S, "tail_len": r["tail_len"]}
+
     def export_bart_states(self) -> list:
         """``stan4bart_exportBARTState`` per chain (reference R/stan4bart_fit.R:572-580): byte strings that
         ``attach_stored_samplers`` turns back into predict-capable samplers, in this or another process."""
