@@ -488,6 +488,61 @@ typedef struct {
 } s4b_loo_out;
 int S4B_FN(predict_loo)(s4b_sampler* s, const s4b_loo_in* in, s4b_loo_out* out);
 
+/* extension (R: Rhat and n_eff of rstan's summary, for every row instead of the handful of Stan parameters): split R-hat and the effective sample
+ * size per row, with the chains KEPT APART.  The estimators are Stan's compute_potential_scale_reduction / compute_effective_sample_size (Gelman et
+ * al., BDA3 11.4 - 11.5; Geyer 1992), restated here; tests/conv_cases.py holds the numpy model they are tested against.
+ *   chains    every pooled sampler is one chain: `s`, then the peers in their order, each OCCURRENCE of a handle a chain of its own, n_c draws each.
+ *             N0 = min n_c; every chain keeps its FIRST N0 draws.  split = 0: C chains of N = N0 draws.  split = 1 (what the Python layer asks for):
+ *             h = floor(N0 / 2), chain c gives chains 2c (its draws 0 .. h-1) and 2c+1 (its draws N0-h .. N0-1; the middle draw of an odd N0 belongs
+ *             to neither): C chains of N = h draws.  D = C N draws are used.  C <= 256 and at most 16384 pooled draws, else the call is refused.
+ *   series    quantity 0: x(i,k) = predict_summary's v(i,k), link 0 or 1.  quantity 1: x(i,k) = exp(l(i,k) - max_k l(i,k)), l predict_ppd's
+ *             log-likelihood of y_i (rows.link: the response; y, sigma, row_scale, peer_sigma under predict_ppd's rules), the maximum over all
+ *             pooled draws: the likelihood up to a factor, which no output depends on — the series of loo::relative_eff.
+ *   per row   mu_c the chain means, d_c[i] = x - mu_c, q_c = sum_i d_c[i]^2, W = sum_c q_c / (C (N-1)), B' = sum_c (mu_c - mean)^2 / (C-1) (0 for
+ *             C = 1), mean = sum_c mu_c / C, var+ = W (N-1) / N + B'.
+ *               rhat = sqrt(var+ / W), NaN for C = 1
+ *             a_c(t) = sum_{i < N-t} d_c[i] d_c[i+t] / N — divisor N at EVERY lag, Geyer's biased estimator: what the autocovariance of Stan's
+ *             analyze/mcmc headers computes —, rho(0) = 1, rho(t) = 1 - (W - sum_c a_c(t) / C) / var+.  Pairs (e_j, o_j) = (rho(2j), rho(2j+1)),
+ *             P_j = e_j + o_j.  J = the first j with 2j + 1 >= N - 4 or not P_j > 0.  P'_0 = P_0, P'_j = min(P'_{j-1}, P_j) for 0 < j < J.
+ *             e'_J = 1 for J = 0, else e_J where P_J >= 0 and 0 otherwise; r = e_J where e_J > 0 and 0 otherwise (the raw value, J = 0: 1).
+ *               tau = -1 + 2 (sum_{j<J} P'_j + e'_J) + r,  ess = min(D / tau, D log10 D)
+ *               mean = the mean of the D draws used,  mcse = sd / sqrt(ess), sd^2 = (sum_c q_c + N sum_c (mu_c - mean)^2) / (D - 1)
+ *               n_pairs = J
+ *             Every output of a row is NaN (n_pairs: -1) where N < 4, where a value used is not finite, or where W = 0 (every chain exactly
+ *             constant: Stan tests approximately, this is the exact rule).
+ * Outputs: n_test values each, each may be NULL, at least one is wanted.  Pooling, scratch_bytes, the chunking and the query form (all outputs NULL
+ * or in = NULL: num_samples of `s` alone) are predict_quantiles'.  Everything is checked before anything is launched; a refused call leaves info all
+ * zero.  Two calls return the same bits, on both routes, with live or stored samplers, under any chunking.  DESIGN.md 5.11. */
+typedef struct {
+  s4b_summary_in rows;            /* n_weights 0; link: quantity 0 the link of v, quantity 1 the response (0 continuous, 1 binary) */
+  int32_t quantity;               /* 0: the fitted value; 1: the likelihood of y */
+  int32_t split;                  /* 0: the chains as they are; 1: every chain in two halves */
+  const double* y;                /* quantity 1: n_test responses; quantity 0: NULL */
+  const double* sigma;            /* quantity 1, link 0: one per draw of `s` */
+  const double* row_scale;        /* quantity 1: n_test, or NULL: 1 */
+  int32_t n_peers;
+  s4b_sampler* const* peers;
+  const double* const* peer_dense_coef;
+  const double* const* peer_ell_coef;
+  const double* const* peer_sigma;        /* quantity 1, link 0: [n_peers] vectors (one value per draw of that peer) */
+  int64_t scratch_bytes;
+} s4b_conv_in;
+typedef struct {
+  double* rhat;                   /* n_test each, or NULL */
+  double* ess;
+  double* mean;
+  double* mcse;
+  int32_t* n_pairs;               /* n_test, or NULL */
+  int64_t num_samples;            /* pooled draws S (of which D = n_chains chain_len are used) */
+  int32_t n_chains;               /* C (0 after a query or a refusal) */
+  int32_t chain_len;              /* N */
+  /* what the call did, s4b_quantile_out.info's layout: [0] route of the value kernel (1 LDS-staged, 2 global; 0: nothing was launched), [1] rows per
+   * chunk, [2] chunks, [3] (rows per workgroup of k_chain_rows) << 32 | draws padded to a power of two, [4] nodes of the largest pooled draw,
+   * [5] kernel launches (2 per chunk), [6] bytes of device memory the call allocated, [7] pooled draws */
+  int64_t info[8];
+} s4b_conv_out;
+int S4B_FN(predict_convergence)(s4b_sampler* s, const s4b_conv_in* in, s4b_conv_out* out);
+
 /* The state of a chain BETWEEN TWO GIBBS ITERATIONS as one relocatable byte string: what the next iteration starts from.  It is
  * the hook of the teacher-forced parity tests (state of one implementation injected into the other before every compared
  * transition) and lets a chain continue in another sampler created from the same data; it is not an archive of a fit: the

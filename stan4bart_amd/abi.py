@@ -146,6 +146,17 @@ class LooOut(C.Structure):             # s4b_loo_out
                 ("tail_len", C.c_int32), ("info", C.c_int64 * 8)]
 
 
+class ConvIn(C.Structure):             # s4b_conv_in
+    _fields_ = [("rows", SummaryIn), ("quantity", C.c_int32), ("split", C.c_int32), ("y", c_double_p), ("sigma", c_double_p), ("row_scale", c_double_p),
+                ("n_peers", C.c_int32), ("peers", C.POINTER(C.c_void_p)), ("peer_dense_coef", C.POINTER(c_double_p)),
+                ("peer_ell_coef", C.POINTER(c_double_p)), ("peer_sigma", C.POINTER(c_double_p)), ("scratch_bytes", C.c_int64)]
+
+
+class ConvOut(C.Structure):            # s4b_conv_out
+    _fields_ = [("rhat", c_double_p), ("ess", c_double_p), ("mean", c_double_p), ("mcse", c_double_p), ("n_pairs", C.POINTER(C.c_int32)),
+                ("num_samples", C.c_int64), ("n_chains", C.c_int32), ("chain_len", C.c_int32), ("info", C.c_int64 * 8)]
+
+
 SUMMARY_ROUTES = {"auto": 0, "staged": 1, "global": 2}
 SUMMARY_INFO = ("route", "rows_per_tile", "workgroups", "staging_bytes", "largest_draw_nodes", "launches", "device_bytes", "staging_nodes")
 PD_INFO = SUMMARY_INFO[:7] + ("largest_affected", "total_affected")          # (the last two share info[7]: trees with a rule on a varied predictor)
@@ -154,6 +165,9 @@ CONTRAST_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes"
 PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
 LOO_INFO = QUANTILE_INFO               # (s4b_loo_out.info likewise; rows_per_sort: rows per workgroup of k_loo_rows)
 LOO_OUTPUTS = ("elpd_loo", "pareto_k", "lpd", "ess")
+CONV_INFO = QUANTILE_INFO              # (s4b_conv_out.info likewise; rows_per_sort: rows per workgroup of k_chain_rows)
+CONV_OUTPUTS = ("rhat", "ess", "mean", "mcse", "n_pairs")
+CONV_QUANTITIES = {"ev": 0, "lik": 1}
 PD_GRID_MAX = 64                       # grid points per s4b_partial_dependence call
 
 
@@ -399,6 +413,7 @@ class Sampler:
             "predict_contrast": [vp, C.POINTER(ContrastIn), C.POINTER(ContrastOut)],
             "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
             "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
+            "predict_convergence": [vp, C.POINTER(ConvIn), C.POINTER(ConvOut)],
             "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
         }
         for name, argtypes in sig.items():
@@ -1015,6 +1030,61 @@ class Sampler:
         del keep, hold_d, hold_e, hold_s, spare, yy, sg, rs
         return dict(res, draws=int(out.num_samples), tail_len=int(out.tail_len), info=dict(self.loo_info))
 
+    def predict_convergence(self, x_test: np.ndarray, quantity="ev", split: bool = True, y=None, sigma=None, row_scale=None, peers=(), peer_sigma=None,
+                            peer_dense_coef=None, peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None,
+                            ell_coef=None, link: int = 0, outputs=CONV_OUTPUTS, route="auto", stage_nodes: int = 0, scratch_bytes: int = 0) -> dict:
+        """``s4b_predict_convergence``: split R-hat and the effective sample size per row with the chains kept apart — this sampler and every one of
+        ``peers`` (each occurrence of a handle) is one chain, cut to the shortest and, with ``split``, halved.  ``quantity`` "ev" (0): the fitted
+        value under ``link``; "lik" (1): the likelihood of ``y`` with ``predict_ppd``'s ``link``, ``sigma`` / ``peer_sigma`` and ``row_scale``.
+        ``outputs``: which of CONV_OUTPUTS are formed.  Returns dict(rhat, ess, mean, mcse [rows] float64, n_pairs [rows] int32 (None where not
+        asked for; NaN / -1 in a row without an answer), draws: the pooled count, chains, chain_len, info: CONV_INFO)."""
+        fn = getattr(self._lib, self._pfx + "predict_convergence", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_convergence")
+
+        def draws(smp):
+            probe = ConvOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        outputs = tuple(outputs)
+        self.conv_info = dict(zip(CONV_INFO, [0] * 9))
+        if not outputs or not set(outputs) <= set(CONV_OUTPUTS):          # (no output pointer at all is the library's query form: refused here)
+            raise ValueError(f"outputs must name at least one of {CONV_OUTPUTS}, not {outputs!r}")
+        if isinstance(quantity, str) and quantity not in CONV_QUANTITIES:          # (a number goes to the library as it is)
+            raise ValueError(f"quantity must be one of {tuple(CONV_QUANTITIES)}, not {quantity!r}")
+        peers = list(peers)
+        own = draws(self)
+        rows_in, keep, rows, _ = self._summary_in(own, x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, None, route,
+                                                   stage_nodes, 0)
+
+        def vector(a, n, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+            if a.shape != (n,):
+                raise ValueError(f"{what} must have shape ({n},), not {a.shape}")
+            return a
+
+        pdc, hold_d = _peer_tables(peers, draws, peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
+        pec, hold_e = _peer_tables(peers, draws, peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
+        psg, hold_s = _peer_tables(peers, draws, None if peer_sigma is None else [np.asarray(t, dtype=np.float64).reshape(-1, 1) for t in peer_sigma], 1, "peer_sigma")
+        handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
+        yy, sg, rs = vector(y, rows, "y"), vector(sigma, own, "sigma"), vector(row_scale, rows, "row_scale")
+        res = {k: (np.zeros(rows, dtype=np.int32 if k == "n_pairs" else np.float64) if k in outputs else None) for k in CONV_OUTPUTS}
+        spare = np.zeros(1)          # (no rows: what the library needs to tell the call from a query)
+        arg = ConvIn(rows=rows_in, quantity=int(CONV_QUANTITIES.get(quantity, quantity)), split=int(bool(split)), y=_dp(yy), sigma=_dp(sg), row_scale=_dp(rs),
+                     n_peers=len(peers), peers=handles if peers else None, peer_dense_coef=pdc, peer_ell_coef=pec, peer_sigma=psg,
+                     scratch_bytes=int(scratch_bytes))
+        ptr = {k: ((v if v.size else spare).ctypes.data_as(C.POINTER(C.c_int32)) if k == "n_pairs" else _dp(v if v.size else spare))
+               for k, v in res.items() if v is not None}
+        out = ConvOut(**ptr)
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        w = [int(v) for v in out.info]
+        self.conv_info = dict(zip(CONV_INFO, w[:3] + [w[3] >> 32, w[3] & 0xFFFFFFFF] + w[4:]))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep, hold_d, hold_e, hold_s, spare, yy, sg, rs
+        return dict(res, draws=int(out.num_samples), chains=int(out.n_chains), chain_len=int(out.chain_len), info=dict(self.conv_info))
+
     def profile_leapfrog(self, n_evals: int = 10) -> dict:
         """Per-leapfrog O(N) sums of the hmc_mode 1 path timed with HIP events (measurement hook of the HIP library)."""
         out = (C.c_double * 8)()
@@ -1137,6 +1207,7 @@ class StoredSampler:
     predict_contrast = Sampler.predict_contrast
     predict_ppd = Sampler.predict_ppd
     predict_loo = Sampler.predict_loo
+    predict_convergence = Sampler.predict_convergence
     export_bart_state = Sampler.export_bart_state
     get_kept_trees = Sampler.get_kept_trees
     get_kept_trees_indexed = Sampler.get_kept_trees_indexed

@@ -103,6 +103,14 @@ int S4B_FN(predict_loo)(s4b_sampler* s, const s4b_loo_in* in, s4b_loo_out* out) 
   s->core.predict_loo(in, out, peers.empty() ? nullptr : peers.data());
   S4B_CATCH
 }
+int S4B_FN(predict_convergence)(s4b_sampler* s, const s4b_conv_in* in, s4b_conv_out* out) {
+  S4B_NEED(s, "predict_convergence") S4B_TRY
+  s->core.dev().bind();
+  std::vector<const s4b::SamplerCore<S4B_DEV>*> peers;          // (a NULL handle stays NULL: the core refuses it by its position)
+  if (in && out && in->n_peers > 0 && in->peers) for (int x = 0; x < in->n_peers; ++x) peers.push_back(in->peers[x] ? &in->peers[x]->core : nullptr);
+  s->core.predict_convergence(in, out, peers.empty() ? nullptr : peers.data());
+  S4B_CATCH
+}
 int S4B_FN(export_bart_state)(s4b_sampler* s, void* buf, int64_t cap, int64_t* size) {
   S4B_NEED(s, "exportBARTState") S4B_TRY s->core.dev().bind(); if (!size) throw std::invalid_argument("exportBARTState: NULL size pointer"); *size = s->core.export_state(buf, cap); S4B_CATCH
 }

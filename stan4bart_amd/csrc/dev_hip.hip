@@ -1630,6 +1630,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 #include "dev_quantile.inc"
 #include "dev_ppd.inc"
 #include "dev_loo.inc"
+#include "dev_conv.inc"
 #include "dev_contrast.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
@@ -2744,6 +2745,8 @@ class DevHip {
   void predict_ppd(const PpdCall& c) { ppd_run(stream_, a_.P, c, launches_); }
   // s4b_predict_loo (dev_loo.inc), likewise
   void predict_loo(const LooCall& c) { loo_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_convergence (dev_conv.inc), likewise
+  void predict_convergence(const ConvCall& c) { conv_run(stream_, a_.P, c, launches_); }
 
   // ---- Stan inputs
   void stan_inputs(int mode, bool wantTrain, double* cX, double* cZ, double* s0, double* trainOut) {

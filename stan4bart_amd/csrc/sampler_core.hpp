@@ -139,6 +139,20 @@ struct LooCall {
   double* elpd; double* khat; double* lpd; double* ess;                  // [nT] each
 };
 
+// does the device layer form split R-hat and the effective sample size per row (s4b_predict_convergence)?  As has_predict_loo.
+template <class D, class = void> struct has_predict_convergence : std::false_type {};
+template <class D> struct has_predict_convergence<D, std::void_t<decltype(&D::predict_convergence)>> : std::true_type {};
+// one s4b_predict_convergence call as the device layer sees it: the rows as QuantileCall.rows (quantity 1: link is the response, as LooCall), the
+// chains after the cut and the split as their first draws inside the pooled row and one common length, each output NULL where it was not asked for
+struct ConvCall {
+  SummaryCall rows;
+  int quantity;                                                          // 0: the fitted value, 1: the likelihood of y
+  const double* y; const double* sigma; const double* rowScale;          // quantity 1: [nT]; [S] or NULL (link 1); [nT] or NULL
+  int numChains, chainLen; const int32_t* chainStart;                    // C, N, [C]
+  int64_t scratchBytes;
+  double* rhat; double* ess; double* mean; double* mcse; int32_t* nPairs;          // [nT] each
+};
+
 template <class Dev>
 class SamplerCore {
  public:
@@ -868,6 +882,67 @@ class SamplerCore {
       out->num_samples = S; out->tail_len = c.tailLen;
       return S;
     } else throw std::invalid_argument("predict_loo: this device layer has no PSIS-LOO kernels (the read-out is formed by the HIP library only)");
+  }
+  // the chains of s4b_predict_convergence: `lens` the kept draws of the pooled samplers in pooled order.  Every chain keeps its first N0 = min lens
+  // draws; split: its first and its last floor(N0 / 2) of those.  Returns the common length N, the first draws inside the pooled row in `start`.
+  static int conv_chains(const std::vector<int64_t>& lens, bool split, std::vector<int32_t>& start) {
+    const int64_t n0 = *std::min_element(lens.begin(), lens.end()), h = n0 / 2;
+    int64_t at = 0;
+    start.clear();
+    for (int64_t n : lens) {
+      start.push_back((int32_t)at);
+      if (split) start.push_back((int32_t)(at + n0 - h));
+      at += n;
+    }
+    return (int)(split ? h : n0);
+  }
+  // s4b_predict_convergence: split R-hat, the effective sample size, the pooled mean and its Monte-Carlo standard error per row with the chains kept
+  // apart — every pooled sampler one chain.  Pooled and validated like predict_loo, before any launch.
+  int64_t predict_convergence(const s4b_conv_in* in, s4b_conv_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_convergence: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own; out->n_chains = 0; out->chain_len = 0;
+    if (!in || (!out->rhat && !out->ess && !out->mean && !out->mcse && !out->n_pairs)) return own;          // query
+    if constexpr (has_predict_convergence<Dev>::value) {
+      const std::string who = "predict_convergence";
+      const s4b_summary_in* rw = &in->rows;
+      if (rw->n_weights != 0) throw std::invalid_argument(who + ": n_weights must be 0 (every output is per row), not " + std::to_string(rw->n_weights));
+      check_summary_rows(rw, who, 0);
+      if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
+      if (in->quantity != 0 && in->quantity != 1) throw std::invalid_argument(who + ": quantity must be 0 (the fitted value) or 1 (the likelihood of y), not " + std::to_string(in->quantity));
+      if (in->split != 0 && in->split != 1) throw std::invalid_argument(who + ": split must be 0 or 1, not " + std::to_string(in->split));
+      if (in->quantity == 1 && !in->y) throw std::invalid_argument(who + ": NULL y (quantity 1 is the likelihood of the responses)");
+      if (in->quantity == 0 && in->y) throw std::invalid_argument(who + ": quantity 0 takes no y");
+      const int64_t nT = rw->n_test;
+      const int np = in->n_peers;
+      const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
+      const int64_t numChains = (int64_t)(np + 1) * (in->split ? 2 : 1);
+      if (numChains > 256) throw std::invalid_argument(who + ": " + std::to_string(numChains) + " chains, at most 256 (" + std::to_string(np + 1) + " pooled samplers" + (in->split ? ", each split in two)" : ")"));
+      std::vector<double> sigma;
+      if (in->quantity == 1) check_responses(who, rw, in->y, in->sigma, in->peer_sigma, in->row_scale, np, peers, S, sigma);
+      std::vector<int64_t> lens{own};
+      for (int x = 0; x < np; ++x) lens.push_back((int64_t)peers[x]->keptScale_.size() / 2);
+      std::vector<int32_t> start;
+      const int N = conv_chains(lens, in->split != 0, start);
+      std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
+      bin_matrix(rw->x_test, (size_t)nT, xb);
+      ConvCall c{};
+      c.rows = summary_call(rw, xb, own); c.rows.info = out->info; c.rows.G = 0; c.rows.weights = nullptr;
+      c.quantity = in->quantity;
+      if (in->quantity == 1) { c.y = in->y; c.sigma = rw->link == 0 ? sigma.data() : nullptr; c.rowScale = rw->link == 0 ? in->row_scale : nullptr; }
+      c.numChains = (int)numChains; c.chainLen = N; c.chainStart = start.data(); c.scratchBytes = in->scratch_bytes;
+      c.rhat = out->rhat; c.ess = out->ess; c.mean = out->mean; c.mcse = out->mcse; c.nPairs = out->n_pairs;
+      DrawPool pool;
+      pool_concat(c.rows, pool, rw, xb, np, peers, in->peer_dense_coef, in->peer_ell_coef, S);
+      if (N < 1) {          // a chain of one draw, split: nothing to launch, every row without an answer
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (double* o : {out->rhat, out->ess, out->mean, out->mcse}) if (o) std::fill(o, o + nT, nan);
+        if (out->n_pairs) std::fill(out->n_pairs, out->n_pairs + nT, -1);
+      } else dev_.predict_convergence(c);
+      out->num_samples = S; out->n_chains = (int32_t)numChains; out->chain_len = N;
+      return S;
+    } else throw std::invalid_argument("predict_convergence: this device layer has no chain kernels (the read-out is formed by the HIP library only)");
   }
   // ---- sampler state as a byte string (layout: include/stan4bart_amd.h, s4b_get_state)
   int64_t get_state(void* buf, int64_t cap) {

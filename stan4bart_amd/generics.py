@@ -721,6 +721,73 @@ class Stan4bartFit:
                 "se": float(np.sqrt(rows * np.var(r["elpd_loo"], ddof=1))) if rows > 1 else float("nan"),
                 "k_threshold": float(thr), "n_high_k": int(np.sum(r["pareto_k"] > thr)), "draws": S, "tail_len": r["tail_len"]}
 
+    # ------------------------------------------------------------------ predict_convergence
+    def predict_convergence(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, type: str = "ev", quantity: str = "ev",
+                            y=None, obs_weights=None, split: bool = True, rhat_threshold: float = 1.01, sample_new_levels: bool = True,
+                            seed: Optional[int] = None):
+        """``Rhat`` and ``n_eff`` for every row: split R-hat and the effective sample size (Stan's estimators) of the rows' draws with the chains
+        kept apart, read out on the device without the [rows x draws] matrix, in ONE pooled call (``s4b_predict_convergence``: the first chain's
+        sampler with the others as its peers, every chain cut to the shortest and, with ``split``, halved).  ``quantity`` "ev": the series is
+        ``predict_summary``'s value (``type`` "ev" or "indiv.bart"); "lik": the likelihood of the responses ``y`` [rows] as ``predict_loo`` forms
+        it (sd = sigma sqrt(1 / obs_weights), or Bernoulli-probit) — the series of ``loo::relative_eff``.  Per row: ``rhat``, ``ess``, ``mean``,
+        ``mcse`` (the Monte-Carlo standard error of ``mean``), ``n_pairs`` (autocorrelation pairs Geyer's sequence kept); NaN / -1 where a row has
+        no answer (fewer than 4 draws per chain, a value that is not finite, every chain constant).  Over the rows: ``rhat_max``, ``n_high_rhat``
+        (rows above ``rhat_threshold``), ``ess_min``; ``chains``, ``chain_len``, ``draws`` (chains x chain_len, the draws used).  "lik" adds
+        ``r_eff = ess / draws`` per row.  Needs bart_args keepTrees."""
+        if quantity not in ("ev", "lik"):
+            raise ValueError(f"'quantity' must be one of ev, lik, not {quantity!r}")
+        if type == "ppd":
+            raise ValueError("predict_convergence does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if quantity == "lik" and type != "ev":
+            raise ValueError("quantity 'lik' is the likelihood of y under the whole prediction: 'type' must be ev")
+        if not self.samplers:
+            raise ValueError("predict_convergence requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_convergence needs x_bart, the rows of the BART predictors")
+        if quantity == "lik" and y is None:
+            raise ValueError("predict_convergence: quantity 'lik' needs y, the responses of the rows")
+        if quantity == "ev" and y is not None:
+            raise ValueError("predict_convergence: quantity 'ev' takes no y (quantity 'lik' is the likelihood of y)")
+        if quantity == "ev" and obs_weights is not None:
+            raise ValueError("predict_convergence: quantity 'ev' takes no obs_weights")
+        if not (np.ndim(rhat_threshold) == 0 and float(rhat_threshold) >= 1.0):
+            raise ValueError(f"'rhat_threshold' must be one value >= 1, not {rhat_threshold!r}")
+        x_bart = np.asarray(x_bart, dtype=np.float64)
+        rows = x_bart.shape[0]
+        lik = quantity == "lik"
+        binary = self.family == "binomial"
+        row_scale = None
+        if lik:
+            y = np.asarray(y, dtype=np.float64)
+            if y.shape != (rows,):
+                raise ValueError(f"y must have shape [{rows}], not {y.shape}")
+            if obs_weights is not None:
+                w = np.asarray(obs_weights, dtype=np.float64)
+                if w.shape != (rows,) or not np.all(np.isfinite(w) & (w > 0.0)):
+                    raise ValueError(f"obs_weights must be {rows} finite values > 0")
+                row_scale = 1.0 / np.sqrt(w)                         # reference R/generics.R:452-459: sd = sigma sqrt(1 / w)
+        need_sigma = lik and not binary
+        sig = self.stan[self.par_names.index("aux.1")] if need_sigma else None          # [iter, chain]
+        linear = self._summary_linear(type, X, groups, offset, sample_new_levels, np.random.default_rng(seed))
+        first, others = linear(0), [linear(c) for c in range(1, len(self.samplers))]
+        r = self.samplers[0].predict_convergence(x_bart, quantity=quantity, split=bool(split), y=y if lik else None,
+                                                 sigma=sig[:, 0] if need_sigma else None, row_scale=row_scale, peers=self.samplers[1:],
+                                                 peer_sigma=[sig[:, c] for c in range(1, len(self.samplers))] if need_sigma else None,
+                                                 peer_dense_coef=None if first["dense"] is None else [a["dense_coef"] for a in others],
+                                                 peer_ell_coef=None if first["ell_index"] is None else [a["ell_coef"] for a in others], **first)
+        used = r["chains"] * r["chain_len"]
+        with np.errstate(invalid="ignore"):
+            high = int(np.sum(r["rhat"] > float(rhat_threshold)))
+        fin_r, fin_e = r["rhat"][np.isfinite(r["rhat"])], r["ess"][np.isfinite(r["ess"])]
+        out = {"rhat": r["rhat"], "ess": r["ess"], "mean": r["mean"], "mcse": r["mcse"], "n_pairs": r["n_pairs"],
+               "rhat_max": float(fin_r.max()) if len(fin_r) else float("nan"), "n_high_rhat": high,
+               "ess_min": float(fin_e.min()) if len(fin_e) else float("nan"), "chains": r["chains"], "chain_len": r["chain_len"], "draws": used}
+        if lik:
+            out["r_eff"] = r["ess"] / used if used else np.full(rows, np.nan)
+        return out
+
     def export_bart_states(self) -> list:
         """``stan4bart_exportBARTState`` per chain (reference R/stan4bart_fit.R:572-580): byte strings that
         ``attach_stored_samplers`` turns back into predict-capable samplers, in this or another process."""
