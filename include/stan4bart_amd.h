@@ -382,6 +382,56 @@ typedef struct {
 } s4b_contrast_out;
 int S4B_FN(predict_contrast)(s4b_sampler* s, const s4b_contrast_in* in, s4b_contrast_out* out);
 
+/* extension (R: the group-by over the rows of extract(fit) or of samples.icate — the average fitted value of every school, the average treatment
+ * effect of every site with its interval and the probability that it is positive — formed on the device): PER-LEVEL sums or means of the rows' values
+ * per pooled draw, summarised over the draws.  Row i belongs to level level[i] in [0, n_levels) and carries the weight w_i >= 0 (every w_i = 1 with
+ * arms.rows.n_weights = 0, weights[i] with n_weights = 1).  With the S pooled draws of `s` and its peers
+ *     a(l,k) = sum_{i : level[i] = l} w_i x(i,k),     x = v(z_1) (n_arms 1: predict_quantiles' value) or v(z_1) - v(z_0) (n_arms 2: predict_contrast's d)
+ *     A(l,k) = a(l,k) (statistic 0, the sum) or a(l,k) / W_l, W_l = sum_{i : level[i] = l} w_i (statistic 1, the mean)
+ * THE ROWS OF A LEVEL ARE CONTIGUOUS: `level` is non-decreasing (a caller with labels in any order sorts its rows by a stable sort first; the Python
+ * binding does).  The order of the additions is fixed and is part of the interface: the rows are cut into slabs of 64 (rows 0..63, 64..127, ...,
+ * whatever the chunking); a(l,k) is the left fold, over the slabs the level touches in ascending order, of the slab's partial; a partial is the left
+ * fold, over the level's rows in the slab in row order, of w_i x(i,k) (without weights: of x(i,k)); the first term of a fold is taken as it is.  No
+ * floating-point atomics, no data-dependent order: the result does not depend on the chunking, the route, or live versus stored samplers, and a
+ * level of one row with weight 1 is that row's value bit for bit.  W_l and count[l] are formed on the host in row order, in double.
+ * `arms` is predict_contrast's input: the rows, arm 0, probs (0 .. 16), peers, scratch_bytes mean what they mean there; with n_arms 1 every arm-0
+ * pointer must be NULL.  Per level:
+ *   mean[l], m2[l]      mean and sum of squared deviations of A(l, .) over the S draws (two passes, as predict_contrast forms a row's)
+ *   quantiles[j, l]     R's type 7 quantiles of A(l, .), prob-major: quantiles[j * n_levels + l]
+ *   p_above[l]          #{k : A(l,k) > threshold} / S (strict; needs has_threshold; +-inf allowed, NaN refused)
+ *   weight[l], count[l] W_l and the rows of the level
+ *   draws[l, k]         A itself, level-major: draws[l * S + k]
+ * A level without rows, or with W_l = 0 under statistic 1, gets NaN in every floating output (weight[l] stays 0); a level whose weights are all 0
+ * under statistic 0 gets exact zeros.  The level matrix (8 n_levels S bytes) stays on the device for the call: it may be at most
+ * S4B_GROUPS_LEVEL_BYTES_MAX, or level_bytes where that is given and smaller; a caller with more levels splits them into consecutive ranges (a range
+ * of levels is a slice of the sorted rows).  Refused before anything is launched, info left all zero: a decreasing label, a label outside
+ * [0, n_levels), a negative or non-finite weight, n_arms outside {1, 2}, an arm-0 pointer with n_arms 1, a statistic outside {0, 1}, 8 n_levels S
+ * above the limit, and whatever predict_contrast refuses.  The peer rules, the limit of 16384 pooled draws and the query form (every output NULL, or
+ * in = NULL: num_samples of `s` alone) are predict_quantiles'.  Device memory: DESIGN.md 5.12 (no term grows with n_test x S beyond a chunk). */
+#define S4B_GROUPS_LEVEL_BYTES_MAX ((int64_t)1 << 30)   /* 1 GiB: the level matrix of one s4b_predict_groups call at most */
+typedef struct {
+  s4b_contrast_in arms;           /* rows (n_weights 0 or 1), arm 0, probs, peers, scratch_bytes: predict_contrast's meaning */
+  int32_t n_arms;                 /* 1: x = v(z_1), every arm-0 pointer NULL; 2: the contrast */
+  const int32_t* level;           /* n_test, non-decreasing, each in [0, n_levels) */
+  int64_t n_levels;
+  int32_t statistic;              /* 0 sum, 1 mean */
+  int32_t has_threshold; double threshold;
+  int64_t level_bytes;            /* 0, or a limit below the library's own on 8 n_levels S */
+} s4b_groups_in;
+typedef struct {
+  double* mean; double* m2;       /* n_levels each, independently NULL where not wanted */
+  double* quantiles;              /* n_probs x n_levels, prob-major; NULL when n_probs = 0 */
+  double* p_above; double* weight; int64_t* count;   /* n_levels each */
+  double* draws;                  /* n_levels x num_samples, level-major */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did: [0] route of the value kernel (as s4b_contrast_out.info[0]), [1] rows per chunk, [2] chunks, [3] kernel launches (per chunk:
+   * values, k_level_reduce, + k_level_fold where a level of the chunk has edge partials; then k_level_rows, + the sort per 2^20 levels with probs),
+   * [4] bytes of device memory the call allocated, [5] pooled draws, [6] levels with edge partials (those touching more than one slab), [7] levels
+   * whose floating outputs are NaN (no rows, or W_l = 0 under statistic 1) */
+  int64_t info[8];
+} s4b_groups_out;
+int S4B_FN(predict_groups)(s4b_sampler* s, const s4b_groups_in* in, s4b_groups_out* out);
+
 /* extension (R: quantiles and scores of extract(fit, "ppd") against held-out responses, formed on the device): the POSTERIOR PREDICTIVE read-out per row
  * over the draws of `s` and its peers, pooled as predict_quantiles pools them: prediction intervals for NEW OBSERVATIONS and the scores of held-out
  * responses y, without the rows-times-draws matrix.  Row i is a row of the call; k is the pooled draw index (the draws of `s`, then the peers' in peer

@@ -123,6 +123,16 @@ class ContrastOut(C.Structure):        # s4b_contrast_out
                 ("info", C.c_int64 * 8)]
 
 
+class GroupsIn(C.Structure):           # s4b_groups_in
+    _fields_ = [("arms", ContrastIn), ("n_arms", C.c_int32), ("level", c_int32_p), ("n_levels", C.c_int64), ("statistic", C.c_int32),
+                ("has_threshold", C.c_int32), ("threshold", C.c_double), ("level_bytes", C.c_int64)]
+
+
+class GroupsOut(C.Structure):          # s4b_groups_out
+    _fields_ = [("mean", c_double_p), ("m2", c_double_p), ("quantiles", c_double_p), ("p_above", c_double_p), ("weight", c_double_p),
+                ("count", C.POINTER(C.c_int64)), ("draws", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
 class PpdIn(C.Structure):              # s4b_ppd_in
     _fields_ = [("rows", SummaryIn), ("y", c_double_p), ("sigma", c_double_p), ("row_scale", c_double_p), ("noise_key", C.c_uint64),
                 ("n_probs", C.c_int32), ("probs", c_double_p), ("n_peers", C.c_int32), ("peers", C.POINTER(C.c_void_p)),
@@ -162,6 +172,9 @@ SUMMARY_INFO = ("route", "rows_per_tile", "workgroups", "staging_bytes", "larges
 PD_INFO = SUMMARY_INFO[:7] + ("largest_affected", "total_affected")          # (the last two share info[7]: trees with a rule on a varied predictor)
 QUANTILE_INFO = ("route", "rows_per_chunk", "chunks", "rows_per_sort", "padded_draws", "largest_draw_nodes", "launches", "device_bytes", "draws")
 CONTRAST_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "differing_columns", "largest_affected", "total_affected")
+GROUPS_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "edge_levels", "nan_levels")
+GROUPS_STATISTICS = {"sum": 0, "mean": 1}
+GROUPS_LEVEL_BYTES_MAX = 1 << 30       # S4B_GROUPS_LEVEL_BYTES_MAX: the level matrix (8 x levels x pooled draws) of one s4b_predict_groups call at most
 PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
 LOO_INFO = QUANTILE_INFO               # (s4b_loo_out.info likewise; rows_per_sort: rows per workgroup of k_loo_rows)
 LOO_OUTPUTS = ("elpd_loo", "pareto_k", "lpd", "ess")
@@ -411,6 +424,7 @@ class Sampler:
             "partial_dependence": [vp, C.POINTER(PdIn), C.POINTER(PdOut)],
             "predict_quantiles": [vp, C.POINTER(QuantileIn), C.POINTER(QuantileOut)],
             "predict_contrast": [vp, C.POINTER(ContrastIn), C.POINTER(ContrastOut)],
+            "predict_groups": [vp, C.POINTER(GroupsIn), C.POINTER(GroupsOut)],
             "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
             "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
             "predict_convergence": [vp, C.POINTER(ConvIn), C.POINTER(ConvOut)],
@@ -872,6 +886,28 @@ class Sampler:
             probe = ContrastOut()
             smp._check(fn(smp._h, None, C.byref(probe)))
             return int(probe.num_samples)
+        arg, keep, rows, G, S, pr = self._contrast_in(draws, x_test, x_test0, probs, peers, peer_dense_coef, peer_ell_coef, offset, offset0, dense, dense0,
+                                                      dense_coef, ell_index, ell_index0, ell_value, ell_value0, ell_coef, link, weights, route, stage_nodes,
+                                                      scratch_bytes)
+        mean, m2 = (np.zeros(rows), np.zeros(rows)) if per_row else (None, None)
+        avg, q = np.zeros((S, G)), np.zeros((len(pr), rows))
+        spare = np.zeros(1)          # (what a count beyond the library's limits would fill: refused there, which needs a pointer to tell the call from a query)
+        out = ContrastOut(mean=_dp(mean), m2=_dp(m2), average=_dp(avg) if avg.size else (_dp(spare) if G else None),
+                          quantiles=_dp(q) if q.size else (_dp(spare) if len(pr) else None))
+        if not per_row and not G and not len(pr):
+            out.average = _dp(spare)          # (nothing asked for: the library says so)
+        self.contrast_info = dict(zip(CONTRAST_INFO, [0] * 9))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        w = [int(v) for v in out.info]
+        self.contrast_info = dict(zip(CONTRAST_INFO, w[:7] + [w[7] >> 32, w[7] & 0xFFFFFFFF]))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep, spare
+        return dict(mean=mean, m2=m2, average=avg, quantiles=q, draws=int(out.num_samples), info=dict(self.contrast_info))
+
+    def _contrast_in(self, draws, x_test, x_test0, probs, peers, peer_dense_coef, peer_ell_coef, offset, offset0, dense, dense0, dense_coef, ell_index,
+                     ell_index0, ell_value, ell_value0, ell_coef, link, weights, route, stage_nodes, scratch_bytes):
+        """The ``s4b_contrast_in`` of a ``predict_contrast`` or ``predict_groups`` call; ``draws(sampler)`` is a sampler's kept draw count:
+        (struct, what it points into, rows, weight vectors, pooled draws, probs)."""
         pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
         if pr.ndim != 1:
             raise ValueError(f"probs must be a vector, not shape {pr.shape}")
@@ -900,23 +936,93 @@ class Sampler:
         pec, hold_e = _peer_tables(peers, draws, peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
         handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
         S = own + sum(draws(p) for p in peers)
-        mean, m2 = (np.zeros(rows), np.zeros(rows)) if per_row else (None, None)
-        avg, q = np.zeros((S, G)), np.zeros((len(pr), rows))
-        spare = np.zeros(1)          # (what a count beyond the library's limits would fill: refused there, which needs a pointer to tell the call from a query)
         arg = ContrastIn(rows=rows_in, x_test0=_dp(x0), offset0=_dp(off0), dense0=_dp(d0), ell_index0=_ip(ix0), ell_value0=_dp(ev0), n_probs=len(pr),
                          probs=_dp(pr), n_peers=len(peers), peers=handles if peers else None, peer_dense_coef=pdc, peer_ell_coef=pec,
                          scratch_bytes=int(scratch_bytes))
-        out = ContrastOut(mean=_dp(mean), m2=_dp(m2), average=_dp(avg) if avg.size else (_dp(spare) if G else None),
-                          quantiles=_dp(q) if q.size else (_dp(spare) if len(pr) else None))
-        if not per_row and not G and not len(pr):
-            out.average = _dp(spare)          # (nothing asked for: the library says so)
-        self.contrast_info = dict(zip(CONTRAST_INFO, [0] * 9))
+        return arg, [keep, hold_d, hold_e, handles, pdc, pec, x0, off0, d0, ix0, ev0, pr], rows, G, S, pr
+
+    def groups_draws(self) -> int:
+        """The kept draws of this sampler, as ``s4b_predict_groups``' query form reports them."""
+        probe = GroupsOut()
+        self._check(self._f("predict_groups")(self._h, None, C.byref(probe)))
+        return int(probe.num_samples)
+
+    @staticmethod
+    def group_order(labels):
+        """The stable sort ``predict_groups`` applies to its rows: (order, sorted labels) with ``labels[order]`` non-decreasing and rows of equal
+        label in their given order."""
+        lab = np.asarray(labels)
+        if lab.ndim != 1 or lab.dtype.kind not in "iu":
+            raise ValueError("level must be a vector of integers")
+        order = np.argsort(lab, kind="stable")
+        return order, lab[order]
+
+    def predict_groups(self, x_test: np.ndarray, level, n_levels: int, x_test0=None, n_arms: int = 1, statistic="mean", threshold=None, probs=(),
+                       peers=(), peer_dense_coef=None, peer_ell_coef=None, offset=None, offset0=None, dense=None, dense0=None, dense_coef=None,
+                       ell_index=None, ell_index0=None, ell_value=None, ell_value0=None, ell_coef=None, link: int = 0, weights=None,
+                       outputs=("mean", "m2", "weight", "count"), route="auto", stage_nodes: int = 0, scratch_bytes: int = 0, level_bytes: int = 0,
+                       presorted: bool = False) -> dict:
+        """``s4b_predict_groups``: per level l of ``level`` (an integer in [0, n_levels) per row, in ANY order) and per pooled draw the weighted sum
+        (``statistic`` "sum") or mean ("mean") of the rows' values — ``n_arms`` 1: ``predict_quantiles``' value, 2: ``predict_contrast``'s d, the
+        arms given as there — and over the draws its mean, m2, the ``probs`` quantiles and, with a ``threshold``, the share of the draws strictly
+        above it.  ``weights`` None (1) or [rows], non-negative.  The library wants the rows of a level contiguous: every row-side array is permuted
+        here by a stable sort of ``level`` (``presorted`` True hands the rows down as they are; a decreasing label is then refused by the
+        library).  ``outputs`` names what is formed besides quantiles (with probs) and p_above (with a threshold): any of "mean", "m2",
+        "weight", "count", "draws" ([levels x pooled draws]).  ``level_bytes`` lowers the limit on 8 x levels x pooled draws
+        (GROUPS_LEVEL_BYTES_MAX).  Returns a dict of the outputs in level order (None where not formed), ``draws_pooled`` and info: GROUPS_INFO."""
+        fn = getattr(self._lib, self._pfx + "predict_groups", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_groups")
+
+        def draws(smp):
+            probe = GroupsOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        unknown = set(outputs) - {"mean", "m2", "weight", "count", "draws"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        lab = np.asarray(level)
+        if lab.ndim != 1 or lab.dtype.kind not in "iu" or len(lab) != np.shape(x_test)[0]:
+            raise ValueError("level must hold one integer per row of x_test")
+        if len(lab) and (lab.min() < -2 ** 31 or lab.max() >= 2 ** 31):
+            raise ValueError("level does not fit 32 bits")
+        L = int(n_levels)
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.shape != (len(lab),):
+                raise ValueError(f"weights must be [{len(lab)}], not shape {weights.shape}")
+        if not presorted:          # the rows of a level next to one another, in their given order: every row-side array goes through the same permutation
+            order, lab = self.group_order(lab)
+
+            def rows_of(a):
+                return None if a is None else np.asarray(a)[order]
+            x_test, x_test0, offset, offset0, dense, dense0 = (rows_of(a) for a in (x_test, x_test0, offset, offset0, dense, dense0))
+            ell_index, ell_index0, ell_value, ell_value0, weights = (rows_of(a) for a in (ell_index, ell_index0, ell_value, ell_value0, weights))
+        lab = _i32(lab)
+        w = None if weights is None else weights[None, :]
+        arms, keep, rows, _, S, pr = self._contrast_in(draws, x_test, x_test0, probs, peers, peer_dense_coef, peer_ell_coef, offset, offset0, dense, dense0,
+                                                       dense_coef, ell_index, ell_index0, ell_value, ell_value0, ell_coef, link, w, route, stage_nodes,
+                                                       scratch_bytes)
+        n = max(L, 1)
+        res = dict(mean=np.zeros(n) if "mean" in outputs else None, m2=np.zeros(n) if "m2" in outputs else None,
+                   quantiles=np.zeros((len(pr), n)) if len(pr) else None, p_above=np.zeros(n) if threshold is not None else None,
+                   weight=np.zeros(n) if "weight" in outputs else None, count=np.zeros(n, dtype=np.int64) if "count" in outputs else None)
+        # (a level matrix beyond the library's limit is refused there: no host array of that size is made for it)
+        fits = 8 * n * S <= GROUPS_LEVEL_BYTES_MAX
+        res["draws"] = np.zeros((n, S) if fits else 1) if "draws" in outputs else None
+        spare = np.zeros(1)          # (nothing asked for: the library needs a pointer to tell the call from a query)
+        arg = GroupsIn(arms=arms, n_arms=int(n_arms), level=_ip(lab), n_levels=L, statistic=int(GROUPS_STATISTICS.get(statistic, statistic)),
+                       has_threshold=int(threshold is not None), threshold=0.0 if threshold is None else float(threshold), level_bytes=int(level_bytes))
+        out = GroupsOut(mean=_dp(res["mean"]), m2=_dp(res["m2"]), quantiles=_dp(res["quantiles"]), p_above=_dp(res["p_above"]), weight=_dp(res["weight"]),
+                        count=None if res["count"] is None else res["count"].ctypes.data_as(C.POINTER(C.c_int64)), draws=_dp(res["draws"]))
+        if all(v is None for v in res.values()):
+            out.weight = _dp(spare)
+        self.groups_info = dict(zip(GROUPS_INFO, [0] * 8))
         rc = fn(self._h, C.byref(arg), C.byref(out))
-        w = [int(v) for v in out.info]
-        self.contrast_info = dict(zip(CONTRAST_INFO, w[:7] + [w[7] >> 32, w[7] & 0xFFFFFFFF]))          # (all zero after a refusal: nothing was launched)
+        self.groups_info = dict(zip(GROUPS_INFO, (int(v) for v in out.info)))          # (all zero after a refusal: nothing was launched)
         self._check(rc)
-        del keep, hold_d, hold_e, spare, x0, off0, d0, ix0, ev0
-        return dict(mean=mean, m2=m2, average=avg, quantiles=q, draws=int(out.num_samples), info=dict(self.contrast_info))
+        del keep, spare
+        return dict(res, draws_pooled=int(out.num_samples), info=dict(self.groups_info))
 
     def predict_ppd(self, x_test: np.ndarray, probs=(), y=None, sigma=None, row_scale=None, noise_key: int = 0, peers=(), peer_sigma=None,
                     peer_dense_coef=None, peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None, ell_coef=None,
@@ -1205,6 +1311,10 @@ class StoredSampler:
     partial_dependence = Sampler.partial_dependence
     predict_quantiles = Sampler.predict_quantiles
     predict_contrast = Sampler.predict_contrast
+    _contrast_in = Sampler._contrast_in
+    group_order = staticmethod(Sampler.group_order)
+    groups_draws = Sampler.groups_draws
+    predict_groups = Sampler.predict_groups
     predict_ppd = Sampler.predict_ppd
     predict_loo = Sampler.predict_loo
     predict_convergence = Sampler.predict_convergence

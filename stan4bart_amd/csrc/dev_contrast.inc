@@ -159,17 +159,39 @@ __global__ __launch_bounds__(BLOCK) void k_contrast_fold(const double* part, int
   }
 }
 
-// uploads, up to four launches per chunk of rows, the downloads — on `stream`, everything allocated here freed here (summary_run's discipline)
-static void contrast_run(hipStream_t stream, int P, const ContrastCall& c, int64_t& launches) {
+// the rows of a call as k_contrast_values reads them (shared with dev_groups.inc): `walks` false where no tree is walked
+static SummaryCall contrast_rows(const ContrastCall& c, bool& walks) {
   SummaryCall r = c.rows;
-  const bool perRow = r.mean != nullptr;
-  const bool walks = r.link != 0 || c.totalAffected > 0;          // link 0 without an affected tree: only linear parts are read
+  walks = r.link != 0 || c.totalAffected > 0;                     // link 0 without an affected tree: only linear parts are read
   if (!walks) r.route = 2;                                        // (nothing to stage)
   if (!r.link) {                                                  // shared linear parts cancel: not uploaded, not evaluated
     if (!c.offset0) r.offset = nullptr;
     if (!c.dense0) r.M = 0;
     if (!c.ellIndex0 && !c.ellValue0) r.E = 0;
   }
+  return r;
+}
+// what k_contrast_values reads, uploaded: the rows, the tree order, arm 0's side (shared with dev_groups.inc)
+static void contrast_upload(CallBuffers& buf, ContrastDev& a, const ContrastCall& c, const SummaryCall& r, int P, const ReadoutPlan& plan) {
+  const size_t nT = (size_t)r.nT, S = (size_t)r.S;
+  buf.upload_rows(a, r, P, plan.stageNodes);
+  a.order = buf.alloc(c.order, S * (size_t)r.T);
+  a.numBase = buf.alloc(c.numBase, S);
+  if (c.D) a.xb0 = buf.alloc(c.xb0, (size_t)c.D * nT);
+  if (c.offset0) a.offset0 = buf.alloc(c.offset0, nT);
+  if (c.dense0) a.dense0 = buf.alloc(c.dense0, nT * (size_t)r.M);
+  if (c.ellIndex0 || c.ellValue0) {
+    a.ellIndex0 = c.ellIndex0 ? buf.alloc(c.ellIndex0, nT * (size_t)r.E) : a.ellIndex;
+    a.ellValue0 = c.ellValue0 ? buf.alloc(c.ellValue0, nT * (size_t)r.E) : a.ellValue;
+  }
+  a.D = c.D; a.var0 = c.D > 0 ? c.vars[0] : -2; a.var1 = c.D > 1 ? c.vars[1] : -2;          // (-2: no node carries it)
+}
+
+// uploads, up to four launches per chunk of rows, the downloads — on `stream`, everything allocated here freed here (summary_run's discipline)
+static void contrast_run(hipStream_t stream, int P, const ContrastCall& c, int64_t& launches) {
+  bool walks;
+  SummaryCall r = contrast_rows(c, walks);
+  const bool perRow = r.mean != nullptr;
   const ReadoutPlan plan = readout_plan(r, 0, 8, false);          // no reduction space; the workgroups are chosen per chunk
   CallBuffers buf(stream);
   const size_t nT = (size_t)r.nT, S = (size_t)r.S, Q = (size_t)c.Q, G = (size_t)r.G;
@@ -182,16 +204,7 @@ static void contrast_run(hipStream_t stream, int P, const ContrastCall& c, int64
   const int R = std::max(1, QT_SORT / Sp);
   const size_t sortLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT);
   ContrastDev a{};
-  buf.upload_rows(a, r, P, plan.stageNodes);
-  a.order = buf.alloc(c.order, S * (size_t)r.T);
-  a.numBase = buf.alloc(c.numBase, S);
-  if (c.D) a.xb0 = buf.alloc(c.xb0, (size_t)c.D * nT);
-  if (c.offset0) a.offset0 = buf.alloc(c.offset0, nT);
-  if (c.dense0) a.dense0 = buf.alloc(c.dense0, nT * (size_t)r.M);
-  if (c.ellIndex0 || c.ellValue0) {
-    a.ellIndex0 = c.ellIndex0 ? buf.alloc(c.ellIndex0, nT * (size_t)r.E) : a.ellIndex;
-    a.ellValue0 = c.ellValue0 ? buf.alloc(c.ellValue0, nT * (size_t)r.E) : a.ellValue;
-  }
+  contrast_upload(buf, a, c, r, P, plan);
   a.vals = buf.alloc<double>(nullptr, (size_t)C * S);
   if (perRow) { a.mean = buf.alloc<double>(nullptr, nT); a.m2 = buf.alloc<double>(nullptr, nT); }
   if (G) {
@@ -200,7 +213,7 @@ static void contrast_run(hipStream_t stream, int P, const ContrastCall& c, int64
     a.average = buf.alloc<double>(nullptr, S * G);
   }
   if (Q) { a.probs = buf.alloc(c.probs, Q); a.quantiles = buf.alloc<double>(nullptr, Q * nT); }
-  a.G = r.G; a.D = c.D; a.var0 = c.D > 0 ? c.vars[0] : -2; a.var1 = c.D > 1 ? c.vars[1] : -2;          // (-2: no node carries it)
+  a.G = r.G;
   a.Q = c.Q; a.Sp = Sp; a.R = R;
   if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_contrast_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
   if (Q) HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortLds));

@@ -1632,6 +1632,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 #include "dev_loo.inc"
 #include "dev_conv.inc"
 #include "dev_contrast.inc"
+#include "dev_groups.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
 static void use_device(int device) {
@@ -2741,6 +2742,8 @@ class DevHip {
   void predict_quantiles(const QuantileCall& c) { quantile_run(stream_, a_.P, c, launches_); }
   // s4b_predict_contrast (dev_contrast.inc), likewise
   void predict_contrast(const ContrastCall& c) { contrast_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_groups (dev_groups.inc), likewise
+  void predict_groups(const GroupsCall& c) { groups_run(stream_, a_.P, c, launches_); }
   // s4b_predict_ppd (dev_ppd.inc), likewise
   void predict_ppd(const PpdCall& c) { ppd_run(stream_, a_.P, c, launches_); }
   // s4b_predict_loo (dev_loo.inc), likewise

@@ -112,6 +112,21 @@ struct ContrastCall {
   int Q; const double* probs; int64_t scratchBytes; double* quantiles;          // as QuantileCall
 };
 
+// does the device layer form per-level sums and means of the rows' values (s4b_predict_groups)?  As has_predict_contrast.
+template <class D, class = void> struct has_predict_groups : std::false_type {};
+template <class D> struct has_predict_groups<D, std::void_t<decltype(&D::predict_groups)>> : std::true_type {};
+// one s4b_predict_groups call as the device layer sees it: the arms as a ContrastCall (one arm: its rows alone are in use, as QuantileCall.rows; no
+// weights, no per-row output there), the validated non-decreasing levels, the row weights (NULL: 1), the first row of every level (levelStart[L] =
+// nT) and W_l as the host formed them, the levels whose outputs are NaN, each output NULL where it was not asked for
+struct GroupsCall {
+  ContrastCall arms;
+  int nArms; const int32_t* level; int64_t L; int statistic, hasThreshold; double threshold;
+  const double* rowWeights;                            // [nT] or NULL
+  const int64_t* levelStart; const double* levelWeight;          // [L + 1], [L]
+  int64_t nanLevels;
+  double* mean; double* m2; double* quantiles; double* pAbove; double* draws;          // [L], [L], [Q x L], [L], [L x S]
+};
+
 // does the device layer form the posterior predictive read-out over the pooled kept draws (s4b_predict_ppd)?  As has_predict_quantiles.
 template <class D, class = void> struct has_predict_ppd : std::false_type {};
 template <class D> struct has_predict_ppd<D, std::void_t<decltype(&D::predict_ppd)>> : std::true_type {};
@@ -723,73 +738,80 @@ class SamplerCore {
     if constexpr (has_predict_contrast<Dev>::value) {
       const std::string who = "predict_contrast";
       const s4b_summary_in* rw = &in->rows;
-      check_summary_rows(rw, who, 8);
-      if (in->n_probs < 0 || in->n_probs > 16) throw std::invalid_argument(who + ": between 0 and 16 probs per call, not " + std::to_string(in->n_probs));
-      if (in->n_probs > 0 && !in->probs) throw std::invalid_argument(who + ": NULL probs");
-      for (int j = 0; j < in->n_probs; ++j)
-        if (!(in->probs[j] >= 0.0 && in->probs[j] <= 1.0)) throw std::invalid_argument(who + ": prob " + std::to_string(in->probs[j]) + " outside [0, 1]");
-      if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
+      contrast_check_in(who, in, 8);
       if ((out->mean == nullptr) != (out->m2 == nullptr)) throw std::invalid_argument(who + ": mean and m2 are given together or not at all");
       if (rw->n_weights > 0 && !out->average) throw std::invalid_argument(who + ": n_weights > 0 needs average");
       if (in->n_probs > 0 && !out->quantiles) throw std::invalid_argument(who + ": n_probs > 0 needs quantiles");
       if (!out->mean && rw->n_weights == 0 && in->n_probs == 0) throw std::invalid_argument(who + ": nothing asked for (no per-row output, no weights, no probs)");
-      const int64_t nT = rw->n_test;
-      // arm 0: a part of its own only where arm 1 has that part
-      if (in->offset0 && !rw->offset) throw std::invalid_argument(who + ": offset0 given, but arm 1 has no offset");
-      if (in->dense0 && rw->n_dense == 0) throw std::invalid_argument(who + ": dense0 given, but arm 1 has no dense part (n_dense = 0)");
-      if ((in->ell_index0 || in->ell_value0) && rw->n_ell == 0) throw std::invalid_argument(who + ": ell_index0 / ell_value0 given, but arm 1 has no ELL part (n_ell = 0)");
-      if (in->ell_index0)
-        for (size_t x = 0, m = (size_t)nT * (size_t)rw->n_ell; x < m; ++x)
-          if (in->ell_index0[x] < -1 || in->ell_index0[x] >= rw->n_ell_coef)
-            throw std::invalid_argument(who + ": ell_index0 " + std::to_string(in->ell_index0[x]) + " outside [-1, " + std::to_string(rw->n_ell_coef) + ")");
-      if (in->x_test0)
-        for (size_t x = 0, m = (size_t)nT * (size_t)P_; x < m; ++x) if (std::isnan(in->x_test0[x])) throw std::invalid_argument(who + ": x_test0 holds a NaN");
-      const int np = in->n_peers;
-      const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
-      std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
-      bin_matrix(rw->x_test, (size_t)nT, xb);
-      // the differing columns: those whose BINS differ in at least one row (two raw values on the same side of every cut do not differ)
-      std::vector<int32_t> diff;
-      std::vector<uint16_t> xb0;
-      if (in->x_test0) {
-        std::vector<uint16_t> all((size_t)P_ * (size_t)nT);
-        bin_matrix(in->x_test0, (size_t)nT, all);
-        for (int j = 0; j < P_; ++j)
-          if (std::memcmp(all.data() + (size_t)j * (size_t)nT, xb.data() + (size_t)j * (size_t)nT, (size_t)nT * 2) != 0) diff.push_back(j);
-        if (diff.size() > 2) {
-          std::string cols;
-          for (int32_t j : diff) cols += (cols.empty() ? "" : ", ") + std::to_string(j);
-          throw std::invalid_argument(who + ": the arms differ in " + std::to_string(diff.size()) + " BART columns (" + cols + "), at most 2 are supported");
-        }
-        for (int32_t j : diff) xb0.insert(xb0.end(), all.begin() + (size_t)j * (size_t)nT, all.begin() + (size_t)(j + 1) * (size_t)nT);
-      }
       ContrastCall c{};
-      c.rows = summary_call(rw, xb, own); c.rows.info = out->info;
-      c.rows.mean = out->mean; c.rows.m2 = out->m2; c.rows.average = out->average;
-      c.D = (int)diff.size(); c.vars[0] = c.D > 0 ? diff[0] : -1; c.vars[1] = c.D > 1 ? diff[1] : -1; c.xb0 = xb0.data();
-      c.offset0 = in->offset0; c.dense0 = in->dense0; c.ellIndex0 = in->ell_index0; c.ellValue0 = in->ell_value0;
-      c.Q = in->n_probs; c.probs = in->probs; c.scratchBytes = in->scratch_bytes; c.quantiles = out->quantiles;
-      DrawPool pool;
-      pool_concat(c.rows, pool, rw, xb, np, peers, in->peer_dense_coef, in->peer_ell_coef, S);
-      // the tree order of every pooled draw, each sampler's own trees: pd_tree_order with vars = the differing columns (none: nothing is affected)
-      std::vector<int32_t> order, numBase;
-      if (c.D == 0) {
-        order.resize((size_t)(S * T_)); numBase.assign((size_t)S, T_);
-        for (int64_t k = 0; k < S; ++k) for (int t = 0; t < T_; ++t) order[(size_t)(k * T_ + t)] = t;
-      } else {
-        std::vector<int32_t> o, nb;
-        for (int x = -1; x < np; ++x) {
-          int64_t mx = 0, tot = 0;
-          (x < 0 ? this : peers[x])->pd_tree_order(c.D, c.vars, o, nb, mx, tot);
-          order.insert(order.end(), o.begin(), o.end()); numBase.insert(numBase.end(), nb.begin(), nb.end());
-          c.maxAffected = std::max(c.maxAffected, mx); c.totalAffected += tot;
-        }
-      }
-      c.order = order.data(); c.numBase = numBase.data();
+      ArmsHold hold;
+      const int64_t S = contrast_arms(who, in, peers, true, out->info, c, hold);
+      c.rows.mean = out->mean; c.rows.m2 = out->m2; c.rows.average = out->average; c.quantiles = out->quantiles;
       dev_.predict_contrast(c);
       out->num_samples = S;
       return S;
     } else throw std::invalid_argument("predict_contrast: this device layer has no contrast kernels (the contrasts are formed by the HIP library only)");
+  }
+  // s4b_predict_groups: per level of a non-decreasing row labelling the weighted sum or mean of the rows' values per pooled draw — one arm:
+  // predict_quantiles' value, two arms: predict_contrast's d — and of that level series the mean, m2, type-7 quantiles and the share of the draws above
+  // a threshold.  W_l and the counts are formed here, in row order.  Everything is validated here, before any launch.
+  int64_t predict_groups(const s4b_groups_in* in, s4b_groups_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_groups: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in || (!out->mean && !out->m2 && !out->quantiles && !out->p_above && !out->weight && !out->count && !out->draws)) return own;          // query
+    if constexpr (has_predict_groups<Dev>::value) {
+      const std::string who = "predict_groups";
+      const s4b_contrast_in* ar = &in->arms;
+      const s4b_summary_in* rw = &ar->rows;
+      contrast_check_in(who, ar, 1);
+      if (in->n_arms != 1 && in->n_arms != 2) throw std::invalid_argument(who + ": n_arms must be 1 (the fitted value) or 2 (the contrast), not " + std::to_string(in->n_arms));
+      if (in->n_arms == 1 && (ar->x_test0 || ar->offset0 || ar->dense0 || ar->ell_index0 || ar->ell_value0))
+        throw std::invalid_argument(who + ": n_arms = 1 takes no arm-0 pointer (x_test0, offset0, dense0, ell_index0, ell_value0 must be NULL)");
+      if (in->statistic != 0 && in->statistic != 1) throw std::invalid_argument(who + ": statistic must be 0 (the sum) or 1 (the mean), not " + std::to_string(in->statistic));
+      if (in->has_threshold != 0 && in->has_threshold != 1) throw std::invalid_argument(who + ": has_threshold must be 0 or 1");
+      if (in->has_threshold && std::isnan(in->threshold)) throw std::invalid_argument(who + ": the threshold is a NaN");
+      if (out->p_above && !in->has_threshold) throw std::invalid_argument(who + ": p_above needs a threshold");
+      if (ar->n_probs > 0 && !out->quantiles) throw std::invalid_argument(who + ": n_probs > 0 needs quantiles");
+      if (!in->level) throw std::invalid_argument(who + ": NULL level");
+      if (in->n_levels < 1 || in->n_levels > 2147483647) throw std::invalid_argument(who + ": n_levels must lie in [1, 2^31), not " + std::to_string(in->n_levels));
+      if (in->level_bytes < 0) throw std::invalid_argument(who + ": negative level_bytes");
+      const int64_t nT = rw->n_test, L = in->n_levels;
+      for (int64_t i = 0; i < nT; ++i) {
+        const int64_t l = in->level[i];
+        if (l < 0 || l >= L) throw std::invalid_argument(who + ": level " + std::to_string(l) + " of row " + std::to_string(i) + " outside [0, " + std::to_string(L) + ")");
+        if (i > 0 && l < in->level[i - 1]) throw std::invalid_argument(who + ": the levels decrease at row " + std::to_string(i) + " (the rows of a level are contiguous: sort the rows by level, stably)");
+      }
+      if (rw->n_weights)
+        for (int64_t i = 0; i < nT; ++i)
+          if (!(rw->weights[i] >= 0.0) || std::isinf(rw->weights[i])) throw std::invalid_argument(who + ": weight " + std::to_string(rw->weights[i]) + " of row " + std::to_string(i) + " is negative or not finite");
+      GroupsCall g{};
+      ArmsHold hold;
+      const int64_t S = contrast_arms(who, ar, peers, in->n_arms == 2, nullptr, g.arms, hold);
+      const int64_t limit = in->level_bytes > 0 ? std::min<int64_t>(in->level_bytes, S4B_GROUPS_LEVEL_BYTES_MAX) : S4B_GROUPS_LEVEL_BYTES_MAX;
+      if (L > limit / (8 * S))
+        throw std::invalid_argument(who + ": the level matrix of " + std::to_string(L) + " levels x " + std::to_string(S) + " pooled draws exceeds " + std::to_string(limit) + " bytes (split the levels into consecutive ranges, one call each)");
+      // the first row of every level, W_l and the counts: in row order, in double
+      std::vector<int64_t> start((size_t)L + 1, nT);
+      std::vector<double> W((size_t)L, 0.0);
+      for (int64_t i = nT - 1; i >= 0; --i) start[(size_t)in->level[i]] = i;
+      for (int64_t l = L - 1; l >= 0; --l) if (start[(size_t)l] > start[(size_t)l + 1]) start[(size_t)l] = start[(size_t)l + 1];          // (a level without rows starts where the next one does)
+      for (int64_t i = 0; i < nT; ++i) W[(size_t)in->level[i]] += rw->n_weights ? rw->weights[i] : 1.0;
+      for (int64_t l = 0; l < L; ++l) {
+        const int64_t n = start[(size_t)l + 1] - start[(size_t)l];
+        if (n == 0 || (in->statistic == 1 && W[(size_t)l] == 0.0)) ++g.nanLevels;
+        if (out->weight) out->weight[l] = W[(size_t)l];
+        if (out->count) out->count[l] = n;
+      }
+      g.arms.rows.info = out->info; g.arms.rows.G = 0; g.arms.rows.weights = nullptr;
+      g.nArms = in->n_arms; g.level = in->level; g.L = L; g.statistic = in->statistic; g.hasThreshold = in->has_threshold; g.threshold = in->threshold;
+      g.rowWeights = rw->n_weights ? rw->weights : nullptr; g.levelStart = start.data(); g.levelWeight = W.data();
+      g.mean = out->mean; g.m2 = out->m2; g.quantiles = ar->n_probs > 0 ? out->quantiles : nullptr; g.pAbove = out->p_above; g.draws = out->draws;
+      dev_.predict_groups(g);
+      out->num_samples = S;
+      return S;
+    } else throw std::invalid_argument("predict_groups: this device layer has no level kernels (the per-level read-out is formed by the HIP library only)");
   }
   // s4b_predict_ppd: the posterior predictive distribution of new observations at the rows — type-7 quantiles of y_rep = z + sigma row_scale e — and the
   // scores of held-out responses y (log predictive density, mean and squared deviations of the pointwise log-likelihood, PIT), per row over the
@@ -1388,6 +1410,73 @@ class SamplerCore {
     rows.nodes = pool.nodes.data(); rows.numNodes = pool.nodes.size(); rows.treeStart = pool.treeStart.data(); rows.scale = pool.scale.data(); rows.S = S;
     if (M) rows.denseCoef = pool.denseCoef.data();
     if (q) rows.ellCoef = pool.ellCoef.data();
+  }
+  // ---- what s4b_predict_contrast and s4b_predict_groups share: the checks of a s4b_contrast_in and the arms as the device layer takes them
+  // the rows, the probs and the scratch limit
+  void contrast_check_in(const std::string& who, const s4b_contrast_in* in, int maxWeights) const {
+    check_summary_rows(&in->rows, who, maxWeights);
+    if (in->n_probs < 0 || in->n_probs > 16) throw std::invalid_argument(who + ": between 0 and 16 probs per call, not " + std::to_string(in->n_probs));
+    if (in->n_probs > 0 && !in->probs) throw std::invalid_argument(who + ": NULL probs");
+    for (int j = 0; j < in->n_probs; ++j)
+      if (!(in->probs[j] >= 0.0 && in->probs[j] <= 1.0)) throw std::invalid_argument(who + ": prob " + std::to_string(in->probs[j]) + " outside [0, 1]");
+    if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
+  }
+  // what a ContrastCall points into: it must outlive the device call
+  struct ArmsHold { std::vector<uint16_t> xb, xb0; std::vector<int32_t> order, numBase; DrawPool pool; };
+  // arm 0's checks, the peer rules, both arms binned with this sampler's cut points, the differing columns, the pool and the tree order of every pooled
+  // draw.  twoArms false (predict_groups with one arm, whose arm-0 pointers are all NULL): the rows and the pool alone.  Returns the pooled draws.
+  int64_t contrast_arms(const std::string& who, const s4b_contrast_in* in, const SamplerCore* const* peers, bool twoArms, int64_t* info, ContrastCall& c, ArmsHold& h) const {
+    const s4b_summary_in* rw = &in->rows;
+    const int64_t own = (int64_t)keptScale_.size() / 2, nT = rw->n_test;
+    // arm 0: a part of its own only where arm 1 has that part
+    if (in->offset0 && !rw->offset) throw std::invalid_argument(who + ": offset0 given, but arm 1 has no offset");
+    if (in->dense0 && rw->n_dense == 0) throw std::invalid_argument(who + ": dense0 given, but arm 1 has no dense part (n_dense = 0)");
+    if ((in->ell_index0 || in->ell_value0) && rw->n_ell == 0) throw std::invalid_argument(who + ": ell_index0 / ell_value0 given, but arm 1 has no ELL part (n_ell = 0)");
+    if (in->ell_index0)
+      for (size_t x = 0, m = (size_t)nT * (size_t)rw->n_ell; x < m; ++x)
+        if (in->ell_index0[x] < -1 || in->ell_index0[x] >= rw->n_ell_coef)
+          throw std::invalid_argument(who + ": ell_index0 " + std::to_string(in->ell_index0[x]) + " outside [-1, " + std::to_string(rw->n_ell_coef) + ")");
+    if (in->x_test0)
+      for (size_t x = 0, m = (size_t)nT * (size_t)P_; x < m; ++x) if (std::isnan(in->x_test0[x])) throw std::invalid_argument(who + ": x_test0 holds a NaN");
+    const int np = in->n_peers;
+    const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
+    h.xb.resize((size_t)P_ * (size_t)nT);
+    bin_matrix(rw->x_test, (size_t)nT, h.xb);
+    // the differing columns: those whose BINS differ in at least one row (two raw values on the same side of every cut do not differ)
+    std::vector<int32_t> diff;
+    if (in->x_test0) {
+      std::vector<uint16_t> all((size_t)P_ * (size_t)nT);
+      bin_matrix(in->x_test0, (size_t)nT, all);
+      for (int j = 0; j < P_; ++j)
+        if (std::memcmp(all.data() + (size_t)j * (size_t)nT, h.xb.data() + (size_t)j * (size_t)nT, (size_t)nT * 2) != 0) diff.push_back(j);
+      if (diff.size() > 2) {
+        std::string cols;
+        for (int32_t j : diff) cols += (cols.empty() ? "" : ", ") + std::to_string(j);
+        throw std::invalid_argument(who + ": the arms differ in " + std::to_string(diff.size()) + " BART columns (" + cols + "), at most 2 are supported");
+      }
+      for (int32_t j : diff) h.xb0.insert(h.xb0.end(), all.begin() + (size_t)j * (size_t)nT, all.begin() + (size_t)(j + 1) * (size_t)nT);
+    }
+    c.rows = summary_call(rw, h.xb, own); c.rows.info = info;
+    c.D = (int)diff.size(); c.vars[0] = c.D > 0 ? diff[0] : -1; c.vars[1] = c.D > 1 ? diff[1] : -1; c.xb0 = h.xb0.data();
+    c.offset0 = in->offset0; c.dense0 = in->dense0; c.ellIndex0 = in->ell_index0; c.ellValue0 = in->ell_value0;
+    c.Q = in->n_probs; c.probs = in->probs; c.scratchBytes = in->scratch_bytes;
+    pool_concat(c.rows, h.pool, rw, h.xb, np, peers, in->peer_dense_coef, in->peer_ell_coef, S);
+    if (!twoArms) return S;
+    // the tree order of every pooled draw, each sampler's own trees: pd_tree_order with vars = the differing columns (none: nothing is affected)
+    if (c.D == 0) {
+      h.order.resize((size_t)(S * T_)); h.numBase.assign((size_t)S, T_);
+      for (int64_t k = 0; k < S; ++k) for (int t = 0; t < T_; ++t) h.order[(size_t)(k * T_ + t)] = t;
+    } else {
+      std::vector<int32_t> o, nb;
+      for (int x = -1; x < np; ++x) {
+        int64_t mx = 0, tot = 0;
+        (x < 0 ? this : peers[x])->pd_tree_order(c.D, c.vars, o, nb, mx, tot);
+        h.order.insert(h.order.end(), o.begin(), o.end()); h.numBase.insert(h.numBase.end(), nb.begin(), nb.end());
+        c.maxAffected = std::max(c.maxAffected, mx); c.totalAffected += tot;
+      }
+    }
+    c.order = h.order.data(); c.numBase = h.numBase.data();
+    return S;
   }
   // what s4b_predict_summary and s4b_partial_dependence check of their rows (s4b_summary_in) before anything is launched
   void check_summary_rows(const s4b_summary_in* in, const std::string& who, int maxWeights) const {

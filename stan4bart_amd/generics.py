@@ -16,7 +16,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from .abi import PD_GRID_MAX
+from .abi import GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, Sampler
 from .fit import GroupTerm, chain_seeds, hip_sampler_factory, make_sampler_args, make_z_csr, qr_back_transform
 from .rcompat import RRng
 
@@ -542,6 +542,29 @@ class Stan4bartFit:
         pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
         if pr.ndim != 1 or len(pr) > 16 or not np.all((pr >= 0.0) & (pr <= 1.0)):
             raise ValueError(f"'probs' must be a vector of at most 16 values in [0, 1], not {probs!r}")
+        x_bart, x_bart0, kw, peer_kw = self._contrast_arms(x_bart, x_bart0, X, X0, groups, groups0, offset, offset0, treatment, levels, type,
+                                                           sample_new_levels, seed)
+        rows = x_bart.shape[0]
+        if row_weights is None:
+            w = np.full((1, rows), 1.0 / rows)
+        else:
+            w = np.asarray(row_weights, dtype=np.float64)
+            if w.ndim != 2 or w.shape[1] != rows:
+                raise ValueError(f"row_weights must have shape [G, {rows}], not {w.shape}")
+            if not 1 <= w.shape[0] <= 8:
+                raise ValueError(f"row_weights holds {w.shape[0]} weight vectors: between 1 and 8 per call")
+        r = self.samplers[0].predict_contrast(x_bart, x_bart0, probs=pr, weights=w, **peer_kw, **kw)
+        n = r["draws"]
+        sd = np.sqrt(r["m2"] / (n - 1)) if n > 1 else np.full(rows, np.nan)
+        average = r["average"].T                                     # [G, pooled draws], chain after chain
+        if not combine_chains:
+            average = average.reshape(w.shape[0], len(self.samplers), -1).transpose(0, 2, 1)
+        return {"mean": r["mean"], "sd": sd, "average": average, "probs": pr, "quantiles": r["quantiles"], "draws": n}
+
+    def _contrast_arms(self, x_bart, x_bart0, X, X0, groups, groups0, offset, offset0, treatment, levels, type, sample_new_levels, seed):
+        """The arms of a ``predict_contrast`` or ``predict_groups`` call as the pooled sampler call takes them: (x_bart, x_bart0, the keyword arguments
+        of the first chain's sampler — the link, the row side of both arms, its coefficient tables — and those naming the other chains as its peers).
+        Without any arm-0 argument and without ``treatment`` nothing of arm 0 is in them: one arm, formed as ``predict_quantiles`` forms it."""
         x_bart = np.asarray(x_bart, dtype=np.float64)
         rows = x_bart.shape[0]
         if treatment is not None:
@@ -559,14 +582,6 @@ class Stan4bartFit:
                 x_bart, x_bart0 = arm1, arm0
             else:
                 X, X0 = arm1, arm0
-        if row_weights is None:
-            w = np.full((1, rows), 1.0 / rows)
-        else:
-            w = np.asarray(row_weights, dtype=np.float64)
-            if w.ndim != 2 or w.shape[1] != rows:
-                raise ValueError(f"row_weights must have shape [G, {rows}], not {w.shape}")
-            if not 1 <= w.shape[0] <= 8:
-                raise ValueError(f"row_weights holds {w.shape[0]} weight vectors: between 1 and 8 per call")
         ev = type == "ev"
         if ev and X0 is not None and X is None:
             raise ValueError("X0 given without X")
@@ -597,15 +612,108 @@ class Stan4bartFit:
             kw.update(ell_index=ix[:rows], ell_value=val[:rows], ell_coef=ell_coef[0])
             if two:
                 kw.update(ell_index0=ix[rows:], ell_value0=val[rows:])
-        r = self.samplers[0].predict_contrast(x_bart, None if x_bart0 is None else np.asarray(x_bart0, dtype=np.float64), probs=pr, peers=self.samplers[1:],
-                                              peer_dense_coef=None if dense_coef is None else dense_coef[1:],
-                                              peer_ell_coef=None if ell_coef is None else ell_coef[1:], weights=w, **kw)
-        n = r["draws"]
-        sd = np.sqrt(r["m2"] / (n - 1)) if n > 1 else np.full(rows, np.nan)
-        average = r["average"].T                                     # [G, pooled draws], chain after chain
-        if not combine_chains:
-            average = average.reshape(w.shape[0], len(self.samplers), -1).transpose(0, 2, 1)
-        return {"mean": r["mean"], "sd": sd, "average": average, "probs": pr, "quantiles": r["quantiles"], "draws": n}
+        peer_kw = dict(peers=self.samplers[1:], peer_dense_coef=None if dense_coef is None else dense_coef[1:],
+                       peer_ell_coef=None if ell_coef is None else ell_coef[1:])
+        return x_bart, None if x_bart0 is None else np.asarray(x_bart0, dtype=np.float64), kw, peer_kw
+
+    # ------------------------------------------------------------------ predict_groups
+    ROW_SIDE = ("offset", "offset0", "dense", "dense0", "ell_index", "ell_index0", "ell_value", "ell_value0")          # what is permuted with the rows
+
+    @staticmethod
+    def groups_split(n_levels: int, draws: int, limit: int):
+        """The consecutive level ranges [(first, end)] of ``predict_groups``' calls: one call where ``limit`` bytes hold the level matrix (8 bytes
+        per level and pooled draw), else one level fewer per call than they hold: a range that starts inside a slab of 64 rows takes the rows in
+        front of it in that slab along as a level of their own."""
+        per = int(limit) // (8 * int(draws))
+        if per < 1:
+            raise ValueError(f"level_bytes {limit} does not hold one level of {draws} pooled draws ({8 * draws} bytes)")
+        if n_levels <= per:
+            return [(0, n_levels)]
+        if per < 2:
+            raise ValueError(f"level_bytes {limit} holds one level of {draws} pooled draws: a split needs room for two (the rows in front of a range keep a level of their own)")
+        return [(l0, min(n_levels, l0 + per - 1)) for l0 in range(0, n_levels, per - 1)]
+
+    def predict_groups(self, by, x_bart=None, x_bart0=None, X=None, X0=None, groups: Optional[Sequence[GroupTerm]] = None,
+                       groups0: Optional[Sequence[GroupTerm]] = None, offset=None, offset0=None, treatment=None, levels=(1.0, 0.0), type: str = "ev",
+                       row_weights=None, statistic: str = "mean", probs=(0.025, 0.5, 0.975), threshold=None, return_draws: bool = False,
+                       combine_chains: bool = True, sample_new_levels: bool = True, seed: Optional[int] = None, level_bytes: Optional[int] = None):
+        """Per-level averages — the group-by over the rows of ``predict``'s matrix or of ``predict_contrast``'s effects: the average fitted value of
+        every school, the average treatment effect of every site with its interval and the posterior probability that it is positive — formed on
+        the device without a [rows x draws] matrix (``s4b_predict_groups``: the first chain's sampler with the others as its peers).  ``by`` is a
+        label per row (any dtype ``np.unique`` takes, any order) or the NAME of a grouping term in ``groups``, whose level per row is taken.  Any
+        arm-0 argument (suffix 0) or ``treatment`` makes it the contrast of two arms, formed as ``predict_contrast`` forms it; otherwise the one
+        arm's expected value as ``predict_quantiles`` forms it.  ``row_weights`` None (1) or [rows], non-negative; ``statistic`` "mean" (the
+        weighted mean of the level's rows per draw) or "sum".  Where the level matrix (8 bytes per level and pooled draw) exceeds ``level_bytes``
+        (None: the library's 1 GiB) the levels are split into consecutive ranges, one call each: the rows are sorted by level, a range is a slice,
+        and only the rows between the slab edge in front of a range and its first row (63 at most) are walked a second time: that keeps the slabs
+        of the sums where one call has them, so a split returns the bits of one call.  Returns ``levels`` (the unique labels), ``count``, ``weight``, ``mean`` and ``sd`` (ddof 1) over all draws and
+        chains, ``probs`` and ``quantiles`` [Q, L], ``p_above`` (with ``threshold``: the share of the draws strictly above it), ``draws`` (the
+        pooled count) and, with ``return_draws``, ``average`` [L, draws] ([L, iter, chain] with ``combine_chains=False``).  A level whose weights
+        are all 0 has NaN under "mean"."""
+        if type == "ppd":
+            raise ValueError("predict_groups does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("predict_groups requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_groups needs x_bart, the new rows of the BART predictors")
+        if statistic not in GROUPS_STATISTICS:
+            raise ValueError(f"'statistic' must be one of {', '.join(GROUPS_STATISTICS)}, not {statistic!r}")
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or len(pr) > 16 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of at most 16 values in [0, 1], not {probs!r}")
+        if threshold is not None and np.isnan(float(threshold)):
+            raise ValueError("'threshold' is a NaN")
+        rows = np.shape(x_bart)[0]
+        if isinstance(by, str):
+            named = {g.name: g for g in (groups or ())}
+            if by not in named:
+                raise ValueError(f"'by' names the grouping term {by!r}, which is not in 'groups'")
+            by = np.asarray(named[by].levels)
+        by = np.asarray(by)
+        if by.shape != (rows,):
+            raise ValueError(f"'by' must hold one label per row ({rows}), not shape {by.shape}")
+        labels, code = np.unique(by, return_inverse=True)
+        w = None
+        if row_weights is not None:
+            w = np.asarray(row_weights, dtype=np.float64)
+            if w.shape != (rows,) or not np.all(np.isfinite(w)) or np.any(w < 0.0):
+                raise ValueError(f"row_weights must be [{rows}] finite non-negative values")
+        two = treatment is not None or any(a is not None for a in (x_bart0, X0, groups0, offset0))
+        x_bart, x_bart0, kw, peer_kw = self._contrast_arms(x_bart, x_bart0, X, X0, groups, groups0, offset, offset0, treatment, levels, type,
+                                                           sample_new_levels, seed)
+        first = self.samplers[0]
+        order, code = Sampler.group_order(code.reshape(-1))
+        row_side = dict(x_test=x_bart, x_test0=x_bart0, weights=w, **{k: kw.pop(k, None) for k in self.ROW_SIDE})
+        row_side = {k: None if a is None else np.asarray(a)[order] for k, a in row_side.items()}
+        S = first.groups_draws() + sum(p.groups_draws() for p in peer_kw["peers"])
+        L = len(labels)
+        out = dict(mean=np.zeros(L), m2=np.zeros(L), weight=np.zeros(L), count=np.zeros(L, dtype=np.int64), quantiles=np.zeros((len(pr), L)),
+                   p_above=None if threshold is None else np.zeros(L), draws=np.zeros((L, S)) if return_draws else None)
+        start = np.searchsorted(code, np.arange(L + 1))                              # the first sorted row of every level
+        for l0, l1 in self.groups_split(L, S, GROUPS_LEVEL_BYTES_MAX if level_bytes is None else level_bytes):
+            # the sums are folded over slabs of 64 rows counted from a call's first row: a range starts on the slab edge at or in front of its first
+            # row, so that its slabs lie where one call over all rows has them (the same bits); the rows in front, 63 at most, are level 0 and dropped
+            i0, i1 = int(start[l0]), int(start[l1])
+            p0 = i0 - i0 % 64
+            lead = 1 if i0 > p0 else 0
+            lab = np.r_[np.zeros(i0 - p0, dtype=code.dtype), code[i0:i1] - l0 + lead]
+            r = first.predict_groups(level=lab, n_levels=l1 - l0 + lead, n_arms=2 if two else 1, statistic=statistic, threshold=threshold, probs=pr,
+                                     outputs=("mean", "m2", "weight", "count") + (("draws",) if return_draws else ()), presorted=True,
+                                     **{k: None if a is None else a[p0:i1] for k, a in row_side.items()}, **peer_kw, **kw)
+            for k in ("mean", "m2", "weight", "count", "p_above", "draws"):
+                if out[k] is not None:
+                    out[k][l0:l1] = r[k][lead:]
+            if len(pr):
+                out["quantiles"][:, l0:l1] = r["quantiles"][:, lead:]
+        sd = np.sqrt(out["m2"] / (S - 1)) if S > 1 else np.full(L, np.nan)
+        res = {"levels": labels, "count": out["count"], "weight": out["weight"], "mean": out["mean"], "sd": sd, "probs": pr,
+               "quantiles": out["quantiles"], "p_above": out["p_above"], "draws": S}
+        if return_draws:
+            avg = out["draws"]                                                        # [L, pooled draws], chain after chain
+            res["average"] = avg if combine_chains else avg.reshape(L, len(self.samplers), -1).transpose(0, 2, 1)
+        return res
 
     # ------------------------------------------------------------------ predict_ppd
     def predict_ppd(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, y=None, probs=(0.025, 0.5, 0.975),
