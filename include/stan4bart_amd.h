@@ -432,6 +432,64 @@ typedef struct {
 } s4b_groups_out;
 int S4B_FN(predict_groups)(s4b_sampler* s, const s4b_groups_in* in, s4b_groups_out* out);
 
+/* extension (R: posterior summarisation — lm(effect ~ moderators, weights) of every row of t(samples.icate), or of the fitted values, and the posterior
+ * of its coefficients and of its R^2 — formed on the device): the PROJECTION of the rows' values on a small design by weighted least squares PER POOLED
+ * DRAW, summarised over the draws.  Row i carries the design row A(i, .) of n_columns = K entries, 1 <= K <= S4B_PROJECTION_COLUMNS_MAX, row-major
+ * (design[i * K + j]), taken as given: no intercept is added.  Weights w_i >= 0 (every w_i = 1 with arms.rows.n_weights = 0, weights[i] with
+ * n_weights = 1).  With the S pooled draws of `s` and its peers and x(i,k) = v(z_1) (n_arms 1: predict_quantiles' value) or v(z_1) - v(z_0) (n_arms 2:
+ * predict_contrast's d)
+ *     G(j,j') = sum_i w_i A(i,j) A(i,j')      b(j,k) = sum_i w_i A(i,j) x(i,k)      s(k) = sum_i w_i x(i,k)      t(k) = sum_i w_i x(i,k)^2
+ *     W       = sum_i w_i, the host's sum in row order in double (part of the definition, returned as `weight`)
+ *     G = L L' (Cholesky),   beta(., k) = G^-1 b(., k) by the two triangular solves,
+ *     rss(k) = t(k) - sum_j beta(j,k) b(j,k),   tss(k) = t(k) - s(k)^2 / W,   r2(k) = 1 - rss(k) / tss(k)   (NaN where tss(k) == 0)
+ * THE RANK RULE ACTS ON THE NORMAL EQUATIONS: the design is deficient where a pivot d_j = G(j,j) - sum_{p<j} L(j,p)^2 is not above tol G(j,j), before
+ * its square root; tol in [0, 1), 0 meaning the default 1e-10.  G has the square of the design's condition number: columns whose scales differ by
+ * orders of magnitude, or an intercept beside uncentred columns, lose pivots long before the design itself is deficient (the Python binding scales
+ * every column by a power of two, which is exact; Stan4bartFit.predict_projection centres).  A deficient design (info[6] = 1), W == 0 (2) or
+ * n_test == 0 (3) gives NaN in every floating output; nothing is partly filled.
+ * THE ORDER OF THE ADDITIONS is fixed and part of the interface: the rows are cut into slabs of S4B_PROJECTION_SLAB = 128 (rows 0..127, 128..255, ...,
+ * whatever the chunking: a chunk of this call is a multiple of 128 rows); with wx = w_i x(i,k) (x(i,k) itself without weights) a term of b is
+ * A(i,j) wx, of s is wx, of t is wx x(i,k); a moment is the left fold, over the slabs in ascending order, of the slab's partial; a partial is the left
+ * fold, over the slab's rows in row order, of the terms, begun from +0; the first partial of the fold over the slabs is taken as it is; a term and its
+ * addition may be one fused multiply-add.  G is formed on the device by the same reduction with the design's own columns as the values, G(j,j') = sum_i A(i,j) (w_i A(i,j')),
+ * and read for j >= j'.  The factorisation and the substitutions subtract their products in ascending index, rss subtracts beta(j,k) b(j,k) from t(k)
+ * in ascending j.  No floating-point atomics, no data-dependent order: the result does not depend on scratch_bytes, the route, or live versus stored
+ * samplers, bit for bit; multiplying a design column by a power of two divides its coefficient by it bit for bit and leaves everything else unchanged.
+ * `arms` is predict_contrast's input: the rows, arm 0, probs (0 .. 16), peers, scratch_bytes mean what they mean there; with n_arms 1 every arm-0
+ * pointer must be NULL.  Outputs; index K of the summaries is r2's:
+ *   coef[j, k], r2[k]   beta and r2, coef[j * S + k]; small, always returned (both pointers are required)
+ *   mean[l], m2[l]      mean and sum of squared deviations over the S draws (two passes, as predict_groups forms a level's), l <= K
+ *   quantiles[q, l]     R's type 7 quantiles, prob-major: quantiles[q * (K + 1) + l]
+ *   p_above[l]          #{k : value > threshold} / S (strict; needs has_threshold; +-inf allowed, NaN refused)
+ *   weight              W
+ * Refused before anything is launched, info left all zero: K outside [1, 32], K > n_test, a design entry or weight that is not finite, a negative
+ * weight, n_arms outside {1, 2}, an arm-0 pointer with n_arms 1, tol outside [0, 1), a NULL coef or r2, and whatever predict_contrast refuses.  The
+ * peer rules, the limit of 16384 pooled draws and the query form (every output NULL, or in = NULL: num_samples of `s` alone) are predict_quantiles'.
+ * Device memory: DESIGN.md 5.13 (it grows with K S and n_test K; no term grows with n_test x S beyond a chunk). */
+#define S4B_PROJECTION_COLUMNS_MAX 32
+#define S4B_PROJECTION_SLAB 128
+typedef struct {
+  s4b_contrast_in arms;           /* rows (n_weights 0 or 1), arm 0, probs, peers, scratch_bytes: predict_contrast's meaning */
+  int32_t n_arms;                 /* 1: x = v(z_1), every arm-0 pointer NULL; 2: the contrast */
+  int32_t n_columns;              /* K */
+  const double* design;           /* n_test x K, row-major */
+  int32_t has_threshold; double threshold;
+  double tol;                     /* pivot tolerance on the normal equations; 0: 1e-10 */
+} s4b_projection_in;
+typedef struct {
+  double* coef; double* r2;       /* K x num_samples, num_samples: required */
+  double* mean; double* m2;       /* K + 1 each, independently NULL where not wanted */
+  double* quantiles;              /* n_probs x (K + 1), prob-major; NULL when n_probs = 0 */
+  double* p_above;                /* K + 1 */
+  double weight;                  /* W */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did: [0] route of the value kernel (as s4b_contrast_out.info[0]), [1] rows per chunk, [2] chunks, [3] kernel launches (per chunk:
+   * k_proj_reduce and k_proj_fold for G; values, k_proj_reduce, k_proj_fold; then k_proj_solve, k_level_rows, + the sort with probs), [4] bytes of
+   * device memory the call allocated, [5] pooled draws, [6] 0 answered, 1 deficient design, 2 W == 0, 3 no rows, [7] K */
+  int64_t info[8];
+} s4b_projection_out;
+int S4B_FN(predict_projection)(s4b_sampler* s, const s4b_projection_in* in, s4b_projection_out* out);
+
 /* extension (R: quantiles and scores of extract(fit, "ppd") against held-out responses, formed on the device): the POSTERIOR PREDICTIVE read-out per row
  * over the draws of `s` and its peers, pooled as predict_quantiles pools them: prediction intervals for NEW OBSERVATIONS and the scores of held-out
  * responses y, without the rows-times-draws matrix.  Row i is a row of the call; k is the pooled draw index (the draws of `s`, then the peers' in peer

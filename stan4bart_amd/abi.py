@@ -133,6 +133,16 @@ class GroupsOut(C.Structure):          # s4b_groups_out
                 ("count", C.POINTER(C.c_int64)), ("draws", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
 
 
+class ProjectionIn(C.Structure):       # s4b_projection_in
+    _fields_ = [("arms", ContrastIn), ("n_arms", C.c_int32), ("n_columns", C.c_int32), ("design", c_double_p), ("has_threshold", C.c_int32),
+                ("threshold", C.c_double), ("tol", C.c_double)]
+
+
+class ProjectionOut(C.Structure):      # s4b_projection_out
+    _fields_ = [("coef", c_double_p), ("r2", c_double_p), ("mean", c_double_p), ("m2", c_double_p), ("quantiles", c_double_p), ("p_above", c_double_p),
+                ("weight", C.c_double), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
 class PpdIn(C.Structure):              # s4b_ppd_in
     _fields_ = [("rows", SummaryIn), ("y", c_double_p), ("sigma", c_double_p), ("row_scale", c_double_p), ("noise_key", C.c_uint64),
                 ("n_probs", C.c_int32), ("probs", c_double_p), ("n_peers", C.c_int32), ("peers", C.POINTER(C.c_void_p)),
@@ -175,6 +185,9 @@ CONTRAST_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes"
 GROUPS_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "edge_levels", "nan_levels")
 GROUPS_STATISTICS = {"sum": 0, "mean": 1}
 GROUPS_LEVEL_BYTES_MAX = 1 << 30       # S4B_GROUPS_LEVEL_BYTES_MAX: the level matrix (8 x levels x pooled draws) of one s4b_predict_groups call at most
+PROJECTION_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "deficient", "columns")
+PROJECTION_COLUMNS_MAX = 32            # S4B_PROJECTION_COLUMNS_MAX: design columns of one s4b_predict_projection call at most
+PROJECTION_SLAB = 128                  # S4B_PROJECTION_SLAB: rows per slab of the moments' fold
 PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
 LOO_INFO = QUANTILE_INFO               # (s4b_loo_out.info likewise; rows_per_sort: rows per workgroup of k_loo_rows)
 LOO_OUTPUTS = ("elpd_loo", "pareto_k", "lpd", "ess")
@@ -425,6 +438,7 @@ class Sampler:
             "predict_quantiles": [vp, C.POINTER(QuantileIn), C.POINTER(QuantileOut)],
             "predict_contrast": [vp, C.POINTER(ContrastIn), C.POINTER(ContrastOut)],
             "predict_groups": [vp, C.POINTER(GroupsIn), C.POINTER(GroupsOut)],
+            "predict_projection": [vp, C.POINTER(ProjectionIn), C.POINTER(ProjectionOut)],
             "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
             "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
             "predict_convergence": [vp, C.POINTER(ConvIn), C.POINTER(ConvOut)],
@@ -1024,6 +1038,79 @@ class Sampler:
         del keep, spare
         return dict(res, draws_pooled=int(out.num_samples), info=dict(self.groups_info))
 
+    def projection_draws(self) -> int:
+        """The kept draws of this sampler, as ``s4b_predict_projection``'s query form reports them."""
+        probe = ProjectionOut()
+        self._check(self._f("predict_projection")(self._h, None, C.byref(probe)))
+        return int(probe.num_samples)
+
+    @staticmethod
+    def column_scales(design):
+        """Per design column the power of two nearest 1 / rms of the column (1 for a column of zeros): multiplying by it is exact."""
+        a = np.asarray(design, dtype=np.float64)
+        rms = np.sqrt(np.mean(a * a, axis=0)) if a.shape[0] else np.ones(a.shape[1])
+        ok = np.isfinite(rms) & (rms > 0.0)
+        return np.where(ok, np.exp2(-np.rint(np.log2(np.where(ok, rms, 1.0)))), 1.0)
+
+    def predict_projection(self, x_test: np.ndarray, design, x_test0=None, n_arms: int = 1, threshold=None, probs=(), tol: float = 1e-10,
+                           scale_columns: bool = True, peers=(), peer_dense_coef=None, peer_ell_coef=None, offset=None, offset0=None, dense=None,
+                           dense0=None, dense_coef=None, ell_index=None, ell_index0=None, ell_value=None, ell_value0=None, ell_coef=None,
+                           link: int = 0, weights=None, route="auto", stage_nodes: int = 0, scratch_bytes: int = 0) -> dict:
+        """``s4b_predict_projection``: per pooled draw the weighted least-squares coefficients of the rows' values — ``n_arms`` 1:
+        ``predict_quantiles``' value, 2: ``predict_contrast``'s d, the arms given as there — on ``design`` [rows x K], K <= 32, taken as given (no
+        intercept is added), the r2 of that fit, and over the draws the mean, m2, the ``probs`` quantiles and, with a ``threshold``, the share of the
+        draws strictly above it, for every coefficient and (index K) for r2.  ``weights`` None (1) or [rows], non-negative.  ``scale_columns``:
+        every design column is multiplied by the power of two nearest 1 / rms of the column before the call and coef, mean, quantiles (times the
+        scale) and m2 (times its square) are scaled back after it.  That is exact — a power of two changes no significand — and removes scale
+        disparities between the columns from the normal equations, on which ``tol`` acts, at no rounding cost; p_above of a scaled coefficient
+        against a threshold other than 0 is counted here from the rescaled coef (the same strict count).  Returns coef [K x draws], r2 [draws], mean,
+        m2 [K + 1], quantiles [Q x (K + 1)] or None, p_above [K + 1] or None, weight, scale [K], deficient (0 answered, 1 deficient design, 2 the
+        weights sum to 0, 3 no rows: NaN in every floating output), ``draws_pooled`` and info: PROJECTION_INFO."""
+        fn = getattr(self._lib, self._pfx + "predict_projection", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_projection")
+
+        def draws(smp):
+            probe = ProjectionOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        A = np.asarray(design, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] != np.shape(x_test)[0]:
+            raise ValueError(f"design must be [{np.shape(x_test)[0]} x K], one row per row of x_test, not shape {A.shape}")
+        K = A.shape[1]
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.shape != (A.shape[0],):
+                raise ValueError(f"weights must be [{A.shape[0]}], not shape {weights.shape}")
+        scale = self.column_scales(A) if scale_columns else np.ones(K)
+        A = np.ascontiguousarray(A * scale)          # (row-major; exact)
+        w = None if weights is None else weights[None, :]
+        arms, keep, rows, _, S, pr = self._contrast_in(draws, x_test, x_test0, probs, peers, peer_dense_coef, peer_ell_coef, offset, offset0, dense, dense0,
+                                                       dense_coef, ell_index, ell_index0, ell_value, ell_value0, ell_coef, link, w, route, stage_nodes,
+                                                       scratch_bytes)
+        n = max(K, 1)
+        res = dict(coef=np.zeros((n, S)), r2=np.zeros(S), mean=np.zeros(n + 1), m2=np.zeros(n + 1),
+                   quantiles=np.zeros((len(pr), n + 1)) if len(pr) else None, p_above=np.zeros(n + 1) if threshold is not None else None)
+        arg = ProjectionIn(arms=arms, n_arms=int(n_arms), n_columns=K, design=_dp(A), has_threshold=int(threshold is not None),
+                           threshold=0.0 if threshold is None else float(threshold), tol=float(tol))
+        out = ProjectionOut(coef=_dp(res["coef"]), r2=_dp(res["r2"]), mean=_dp(res["mean"]), m2=_dp(res["m2"]), quantiles=_dp(res["quantiles"]),
+                            p_above=_dp(res["p_above"]))
+        self.projection_info = dict(zip(PROJECTION_INFO, [0] * 8))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        self.projection_info = dict(zip(PROJECTION_INFO, (int(v) for v in out.info)))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep
+        if np.any(scale != 1.0):          # back to the caller's columns: beta_j = scale_j x (the scaled column's coefficient)
+            res["coef"] *= scale[:, None]
+            res["mean"][:K] *= scale
+            res["m2"][:K] *= scale * scale
+            if res["quantiles"] is not None:
+                res["quantiles"][:, :K] *= scale
+            if threshold is not None and float(threshold) != 0.0 and not np.isnan(res["p_above"][0]):
+                res["p_above"][:K] = (res["coef"] > float(threshold)).sum(axis=1) / float(S)
+        return dict(res, weight=float(out.weight), scale=scale, deficient=int(out.info[6]), draws_pooled=int(out.num_samples),
+                    info=dict(self.projection_info))
+
     def predict_ppd(self, x_test: np.ndarray, probs=(), y=None, sigma=None, row_scale=None, noise_key: int = 0, peers=(), peer_sigma=None,
                     peer_dense_coef=None, peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None, ell_coef=None,
                     link: int = 0, lpd: bool = True, moments: bool = True, pit: Optional[bool] = None, route="auto", stage_nodes: int = 0,
@@ -1315,6 +1402,9 @@ class StoredSampler:
     group_order = staticmethod(Sampler.group_order)
     groups_draws = Sampler.groups_draws
     predict_groups = Sampler.predict_groups
+    column_scales = staticmethod(Sampler.column_scales)
+    projection_draws = Sampler.projection_draws
+    predict_projection = Sampler.predict_projection
     predict_ppd = Sampler.predict_ppd
     predict_loo = Sampler.predict_loo
     predict_convergence = Sampler.predict_convergence

@@ -1633,6 +1633,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 #include "dev_conv.inc"
 #include "dev_contrast.inc"
 #include "dev_groups.inc"
+#include "readout_projection.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
 static void use_device(int device) {
@@ -2744,6 +2745,8 @@ class DevHip {
   void predict_contrast(const ContrastCall& c) { contrast_run(stream_, a_.P, c, launches_); }
   // s4b_predict_groups (dev_groups.inc), likewise
   void predict_groups(const GroupsCall& c) { groups_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_projection (readout_projection.inc), likewise
+  void predict_projection(const ProjectionCall& c) { projection_run(stream_, a_.P, c, launches_); }
   // s4b_predict_ppd (dev_ppd.inc), likewise
   void predict_ppd(const PpdCall& c) { ppd_run(stream_, a_.P, c, launches_); }
   // s4b_predict_loo (dev_loo.inc), likewise

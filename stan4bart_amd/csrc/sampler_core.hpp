@@ -127,6 +127,20 @@ struct GroupsCall {
   double* mean; double* m2; double* quantiles; double* pAbove; double* draws;          // [L], [L], [Q x L], [L], [L x S]
 };
 
+// does the device layer project the rows' values on a design per pooled draw (s4b_predict_projection)?  As has_predict_groups.
+template <class D, class = void> struct has_predict_projection : std::false_type {};
+template <class D> struct has_predict_projection<D, std::void_t<decltype(&D::predict_projection)>> : std::true_type {};
+// one s4b_predict_projection call as the device layer sees it: the arms as GroupsCall's, the validated design [nT x K] row-major, the row weights
+// (NULL: 1) and W > 0 as the host formed it, the pivot tolerance resolved, coef and r2 always, every other output NULL where it was not asked for
+struct ProjectionCall {
+  ContrastCall arms;
+  int nArms; const double* design; int K;
+  const double* rowWeights; double W, tol;
+  int hasThreshold; double threshold;
+  double* coef; double* r2;                            // [K x S], [S]
+  double* mean; double* m2; double* quantiles; double* pAbove;          // [K + 1], [K + 1], [Q x (K + 1)], [K + 1]: the coefficients, then r2
+};
+
 // does the device layer form the posterior predictive read-out over the pooled kept draws (s4b_predict_ppd)?  As has_predict_quantiles.
 template <class D, class = void> struct has_predict_ppd : std::false_type {};
 template <class D> struct has_predict_ppd<D, std::void_t<decltype(&D::predict_ppd)>> : std::true_type {};
@@ -812,6 +826,77 @@ class SamplerCore {
       out->num_samples = S;
       return S;
     } else throw std::invalid_argument("predict_groups: this device layer has no level kernels (the per-level read-out is formed by the HIP library only)");
+  }
+  // s4b_predict_projection: per pooled draw the weighted least-squares coefficients of the rows' values — one arm: predict_quantiles' value, two arms:
+  // predict_contrast's d — on a design of at most 32 columns, the share of the variation the projection captures, and of those series the mean, m2,
+  // type-7 quantiles and the share of the draws above a threshold.  W is formed here, in row order.  Everything is validated here, before any launch.
+  int64_t predict_projection(const s4b_projection_in* in, s4b_projection_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_projection: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    out->weight = 0.0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in || (!out->coef && !out->r2 && !out->mean && !out->m2 && !out->quantiles && !out->p_above)) return own;          // query
+    if constexpr (has_predict_projection<Dev>::value) {
+      const std::string who = "predict_projection";
+      const s4b_contrast_in* ar = &in->arms;
+      const s4b_summary_in* rw = &ar->rows;
+      const int64_t nT = rw->n_test;
+      const int K = in->n_columns;
+      if (!out->coef || !out->r2) throw std::invalid_argument(who + ": coef and r2 are always returned (NULL pointer)");
+      if (K < 1 || K > S4B_PROJECTION_COLUMNS_MAX)
+        throw std::invalid_argument(who + ": n_columns must lie in [1, " + std::to_string(S4B_PROJECTION_COLUMNS_MAX) + "], not " + std::to_string(K));
+      if (in->n_arms != 1 && in->n_arms != 2) throw std::invalid_argument(who + ": n_arms must be 1 (the fitted value) or 2 (the contrast), not " + std::to_string(in->n_arms));
+      if (in->has_threshold != 0 && in->has_threshold != 1) throw std::invalid_argument(who + ": has_threshold must be 0 or 1");
+      if (in->has_threshold && std::isnan(in->threshold)) throw std::invalid_argument(who + ": the threshold is a NaN");
+      if (out->p_above && !in->has_threshold) throw std::invalid_argument(who + ": p_above needs a threshold");
+      if (!(in->tol >= 0.0 && in->tol < 1.0)) throw std::invalid_argument(who + ": tol must lie in [0, 1) (0: the default 1e-10), not " + std::to_string(in->tol));
+      if (nT < 0) throw std::invalid_argument(who + ": negative n_test");
+      // what answers NaN in every floating output without a launch: `why` goes to info[6]
+      auto unanswered = [&](int64_t S, int64_t why) {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        const size_t L = (size_t)K + 1, Q = (size_t)std::max(0, ar->n_probs);
+        std::fill(out->coef, out->coef + (size_t)K * (size_t)S, nan); std::fill(out->r2, out->r2 + S, nan);
+        if (out->mean) std::fill(out->mean, out->mean + L, nan);
+        if (out->m2) std::fill(out->m2, out->m2 + L, nan);
+        if (out->p_above) std::fill(out->p_above, out->p_above + L, nan);
+        if (out->quantiles) std::fill(out->quantiles, out->quantiles + Q * L, nan);
+        out->info[5] = S; out->info[6] = why; out->info[7] = K; out->num_samples = S;
+        return S;
+      };
+      if (nT == 0) {          // no rows: nothing to project
+        if (ar->n_probs < 0 || ar->n_probs > 16) throw std::invalid_argument(who + ": between 0 and 16 probs per call, not " + std::to_string(ar->n_probs));
+        return unanswered(pool_check(who, rw, ar->n_peers, ar->peers != nullptr, peers, ar->peer_dense_coef, ar->peer_ell_coef), 3);
+      }
+      contrast_check_in(who, ar, 1);
+      if (in->n_arms == 1 && (ar->x_test0 || ar->offset0 || ar->dense0 || ar->ell_index0 || ar->ell_value0))
+        throw std::invalid_argument(who + ": n_arms = 1 takes no arm-0 pointer (x_test0, offset0, dense0, ell_index0, ell_value0 must be NULL)");
+      if (ar->n_probs > 0 && !out->quantiles) throw std::invalid_argument(who + ": n_probs > 0 needs quantiles");
+      if (!in->design) throw std::invalid_argument(who + ": NULL design");
+      if ((int64_t)K > nT) throw std::invalid_argument(who + ": " + std::to_string(K) + " design columns, but only " + std::to_string(nT) + " rows");
+      for (int64_t i = 0; i < nT; ++i)
+        for (int j = 0; j < K; ++j)
+          if (!std::isfinite(in->design[(size_t)i * (size_t)K + (size_t)j]))
+            throw std::invalid_argument(who + ": design entry (" + std::to_string(i) + ", " + std::to_string(j) + ") is not finite");
+      double W = 0.0;          // in row order, in double: part of the definition
+      for (int64_t i = 0; i < nT; ++i) {
+        const double w = rw->n_weights ? rw->weights[i] : 1.0;
+        if (!(w >= 0.0) || std::isinf(w)) throw std::invalid_argument(who + ": weight " + std::to_string(w) + " of row " + std::to_string(i) + " is negative or not finite");
+        W += w;
+      }
+      out->weight = W;
+      ProjectionCall g{};
+      ArmsHold hold;
+      const int64_t S = contrast_arms(who, ar, peers, in->n_arms == 2, nullptr, g.arms, hold);
+      if (W == 0.0) return unanswered(S, 2);
+      g.arms.rows.info = out->info; g.arms.rows.G = 0; g.arms.rows.weights = nullptr;
+      g.nArms = in->n_arms; g.design = in->design; g.K = K; g.rowWeights = rw->n_weights ? rw->weights : nullptr; g.W = W;
+      g.tol = in->tol > 0.0 ? in->tol : 1e-10; g.hasThreshold = in->has_threshold; g.threshold = in->threshold;
+      g.coef = out->coef; g.r2 = out->r2; g.mean = out->mean; g.m2 = out->m2; g.quantiles = ar->n_probs > 0 ? out->quantiles : nullptr; g.pAbove = out->p_above;
+      dev_.predict_projection(g);
+      out->num_samples = S;
+      return S;
+    } else throw std::invalid_argument("predict_projection: this device layer has no projection kernels (the per-draw least squares is formed by the HIP library only)");
   }
   // s4b_predict_ppd: the posterior predictive distribution of new observations at the rows — type-7 quantiles of y_rep = z + sigma row_scale e — and the
   // scores of held-out responses y (log predictive density, mean and squared deviations of the pointwise log-likelihood, PIT), per row over the

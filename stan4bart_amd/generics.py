@@ -16,7 +16,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from .abi import GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, Sampler
+from .abi import GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, PROJECTION_COLUMNS_MAX, Sampler
 from .fit import GroupTerm, chain_seeds, hip_sampler_factory, make_sampler_args, make_z_csr, qr_back_transform
 from .rcompat import RRng
 
@@ -714,6 +714,82 @@ class Stan4bartFit:
             avg = out["draws"]                                                        # [L, pooled draws], chain after chain
             res["average"] = avg if combine_chains else avg.reshape(L, len(self.samplers), -1).transpose(0, 2, 1)
         return res
+
+    # ------------------------------------------------------------------ predict_projection
+    def predict_projection(self, design, x_bart=None, x_bart0=None, X=None, X0=None, groups: Optional[Sequence[GroupTerm]] = None,
+                           groups0: Optional[Sequence[GroupTerm]] = None, offset=None, offset0=None, treatment=None, levels=(1.0, 0.0),
+                           row_weights=None, names=None, intercept: bool = True, center: bool = True, probs=(0.025, 0.5, 0.975), threshold=0.0,
+                           tol: float = 1e-10, type: str = "ev", sample_new_levels: bool = True, seed: Optional[int] = None):
+        """Posterior summarisation: which covariates moderate the effect (or the fitted value), by how much, with an interval.  For every posterior
+        draw the rows' values — any arm-0 argument (suffix 0) or ``treatment`` makes them the contrast of two arms as ``predict_contrast`` forms it,
+        otherwise the one arm's expected value as ``predict_quantiles`` forms it — are projected on ``design`` [rows x columns] by weighted least
+        squares, on the device without a [rows x draws] matrix, in ONE pooled call (``s4b_predict_projection``: the first chain's sampler with the
+        others as its peers).  ``intercept`` prepends a column of ones; ``center`` (with an intercept) subtracts from every other column its
+        weighted mean, returned as ``center``: the slopes are unchanged, the intercept then IS the weighted average value or effect, and the normal
+        equations are better conditioned.  At most 32 columns, the intercept included.  ``row_weights`` None (1) or [rows], non-negative.  The
+        rank rule acts on the normal equations: a pivot of their Cholesky factorisation not above ``tol`` times its diagonal entry makes the design
+        ``deficient`` and every result NaN.  Returns ``names``, ``coef`` [K, draws] (chain after chain), ``mean``, ``sd`` (ddof 1), ``probs``,
+        ``quantiles`` [Q, K] and ``p_above`` [K] (the share of the draws strictly above ``threshold``) per coefficient, ``r2`` [draws] with
+        ``r2_mean`` and ``r2_quantiles`` [Q] (the share of the weighted variation of the rows' values the projection captures, per draw),
+        ``center`` [K], ``weight``, ``deficient``, ``draws`` and ``info``."""
+        if type == "ppd":
+            raise ValueError("predict_projection does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("predict_projection requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_projection needs x_bart, the new rows of the BART predictors")
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or len(pr) > 16 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of at most 16 values in [0, 1], not {probs!r}")
+        if threshold is not None and np.isnan(float(threshold)):
+            raise ValueError("'threshold' is a NaN")
+        if not 0.0 <= float(tol) < 1.0:
+            raise ValueError(f"'tol' must lie in [0, 1), not {tol!r}")
+        rows = np.shape(x_bart)[0]
+        A = np.asarray(design, dtype=np.float64)
+        if A.ndim == 1:
+            A = A[:, None]
+        if A.ndim != 2 or A.shape[0] != rows:
+            raise ValueError(f"'design' must hold one row per row of x_bart ({rows}), not shape {A.shape}")
+        if not np.all(np.isfinite(A)):
+            raise ValueError("'design' holds a value that is not finite")
+        cols = A.shape[1]
+        K = cols + int(bool(intercept))
+        if not 1 <= K <= PROJECTION_COLUMNS_MAX:
+            raise ValueError(f"between 1 and {PROJECTION_COLUMNS_MAX} design columns, the intercept included, not {K}")
+        if K > rows:
+            raise ValueError(f"{K} design columns, the intercept included, but only {rows} rows")
+        if names is None:
+            names = [f"x{j + 1}" for j in range(cols)]
+        names = [str(s) for s in names]
+        if len(names) != cols:
+            raise ValueError(f"'names' must name the {cols} columns of 'design', not {len(names)}")
+        w = None
+        if row_weights is not None:
+            w = np.asarray(row_weights, dtype=np.float64)
+            if w.shape != (rows,) or not np.all(np.isfinite(w)) or np.any(w < 0.0):
+                raise ValueError(f"row_weights must be [{rows}] finite non-negative values")
+        shift = np.zeros(K)
+        if intercept:
+            if center and cols:
+                tot = float(rows) if w is None else float(w.sum())
+                if tot > 0.0:
+                    shift[1:] = (A.sum(axis=0) if w is None else w @ A) / tot
+            A = np.column_stack([np.ones(rows), A - shift[1:]])
+            names = ["(Intercept)"] + names
+        two = treatment is not None or any(a is not None for a in (x_bart0, X0, groups0, offset0))
+        x_bart, x_bart0, kw, peer_kw = self._contrast_arms(x_bart, x_bart0, X, X0, groups, groups0, offset, offset0, treatment, levels, type,
+                                                           sample_new_levels, seed)
+        r = self.samplers[0].predict_projection(x_test=x_bart, design=A, x_test0=x_bart0, n_arms=2 if two else 1, threshold=threshold, probs=pr, tol=tol,
+                                                weights=w, **peer_kw, **kw)
+        S = r["draws_pooled"]
+        sd = np.sqrt(r["m2"][:K] / (S - 1)) if S > 1 else np.full(K, np.nan)
+        q = r["quantiles"] if r["quantiles"] is not None else np.zeros((0, K + 1))
+        return {"names": names, "coef": r["coef"], "mean": r["mean"][:K], "sd": sd, "probs": pr, "quantiles": q[:, :K],
+                "p_above": None if r["p_above"] is None else r["p_above"][:K], "r2": r["r2"], "r2_mean": float(r["mean"][K]), "r2_quantiles": q[:, K],
+                "center": shift, "weight": r["weight"], "deficient": r["deficient"], "draws": S, "info": r["info"]}
 
     # ------------------------------------------------------------------ predict_ppd
     def predict_ppd(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, y=None, probs=(0.025, 0.5, 0.975),
