@@ -490,6 +490,66 @@ typedef struct {
 } s4b_projection_out;
 int S4B_FN(predict_projection)(s4b_sampler* s, const s4b_projection_in* in, s4b_projection_out* out);
 
+/* extension (R: the heterogeneity of the effects — sd(icate), mean(icate > 0), range(icate) of every row of t(samples.icate) — and rstanarm's
+ * bayes_R2, formed on the device): the SPREAD of the rows' values ACROSS THE ROWS within one pooled draw, summarised over the draws.  Every other
+ * read-out summarises along the draws for a fixed row or adds rows linearly per draw; this one reads the distribution over the rows of one draw.
+ * Row i carries the weight w_i >= 0 (every w_i = 1 with arms.rows.n_weights = 0, weights[i] with n_weights = 1).  thresholds[T],
+ * 0 <= T <= S4B_SPREAD_THRESHOLDS_MAX, strictly ascending; +-inf allowed, NaN refused.  With the S pooled draws of `s` and its peers,
+ * x(i,k) = v(z_1) (n_arms 1: predict_quantiles' value) or v(z_1) - v(z_0) (n_arms 2: predict_contrast's d) and
+ * W = sum_i w_i, the host's sum in row order in double (part of the definition, returned as `weight`; W == 0 is refused), the call forms per pooled
+ * draw k the matrix D[m, k] of M = 4 + 2 T statistics:
+ *     m = 0          mean_k = sum_i w_i x(i,k) / W
+ *     m = 1          sd_k = sqrt(M2_k / W),  M2_k = sum_i w_i (x(i,k) - mean_k)^2   (population form; exactly 0 for one row of positive weight)
+ *     m = 2, 3       min_k, max_k over the rows with w_i > 0
+ *     m = 4 + j      share_above[j] = (sum of w_i over the rows with x(i,k) > t_j) / W     (strict)
+ *     m = 4 + T + j  part_above[j]  = (sum of w_i x(i,k) over the rows with x(i,k) > t_j) / W: the part of the mean contributed by the rows above t_j
+ * part_above is always finite; the mean value among the rows above t_j is part_above / share_above, the gain of treating exactly those rows at cost
+ * t_j is part_above - t_j share_above (callers form both; the matrix holds no NaN).  Over the draws, per statistic m:
+ *   mean[m], m2[m]      mean and sum of squared deviations over the S draws (two passes, as predict_groups forms a level's)
+ *   quantiles[q, m]     R's type 7 quantiles, prob-major: quantiles[q * M + m]
+ *   draws[m, k]         D itself, statistic-major: draws[m * S + k] (at most 132 x 16384 doubles)
+ *   weight              W
+ * THE ORDER OF THE ADDITIONS is fixed and part of the interface: no floating-point atomics, no data-dependent order.  The rows are cut into slabs of
+ * S4B_SPREAD_SLAB = 128 (rows 0..127, 128..255, ..., whatever the chunking: a chunk of this call is a multiple of 128 rows), so the result does not
+ * depend on scratch_bytes, the route, or live versus stored samplers, bit for bit.
+ *   Moments.  Per slab, with the shift c = the value of the slab's first row: W_s = fold of w_i, s1 = fold of w_i (x - c), s2 = fold of
+ *   w_i (x - c)^2, left folds in row order from +0 (without weights the terms are 1, x - c, (x - c)^2); a term and its addition may be one fused
+ *   multiply-add.  The slab's partial is (W_s, mean_s = c + s1 / W_s, M2_s = s2 - s1^2 / W_s, clamped at 0).  The partials combine over the slabs in
+ *   ascending order by the pairwise update (Chan, Golub, LeVeque): delta = mean_b - mean_a, W_ab = W_a + W_b, mean = mean_a + delta W_b / W_ab,
+ *   M2 = M2_a + M2_b + delta^2 W_a W_b / W_ab.  A partial with W_s = 0 is skipped; the first partial with positive weight is taken as it is.  The
+ *   shift keeps the second moment from cancelling where the spread is small against the mean.  D divides by the host's W.
+ *   Bins.  bin(x) = #{j : x > t_j} in [0, T].  Per slab and bin, cw[b] = fold of w_i and cs[b] = fold of w_i x in row order from +0; over the slabs
+ *   they are added in ascending order; after the last chunk above_w[j] = sum_{b > j} cw[b] is added from b = T downward, above_s likewise.  Without
+ *   weights cw are counts, exact in double: share_above is count / n_test exactly.
+ *   Extremes are order-free.
+ * Multiplying every weight by a power of two changes no output; one row gives mean = min = max = its value and sd = 0, bit for bit.
+ * `arms` is predict_contrast's input: the rows, arm 0, probs (0 .. 16), peers, scratch_bytes mean what they mean there; with n_arms 1 every arm-0
+ * pointer must be NULL.  Refused before anything is launched, info left all zero: T outside [0, 64], a NaN threshold, thresholds that are not
+ * strictly ascending, n_weights > 1, a negative or non-finite weight, W == 0, n_arms outside {1, 2}, an arm-0 pointer with n_arms 1, bin_index
+ * outside {0, 1, 2}, and whatever predict_contrast refuses.  The peer rules, the limit of 16384 pooled draws and the query form (every output NULL, or
+ * in = NULL: num_samples of `s` alone) are predict_quantiles'.  Device memory: DESIGN.md 5.14 (no term grows with n_test x S beyond a chunk). */
+#define S4B_SPREAD_THRESHOLDS_MAX 64
+#define S4B_SPREAD_SLAB 128
+typedef struct {
+  s4b_contrast_in arms;           /* rows (n_weights 0 or 1), arm 0, probs, peers, scratch_bytes: predict_contrast's meaning */
+  int32_t n_arms;                 /* 1: x = v(z_1), every arm-0 pointer NULL; 2: the contrast */
+  int32_t n_thresholds;           /* T */
+  const double* thresholds;       /* T, strictly ascending; NULL with T = 0 */
+  int32_t bin_index;              /* how the kernel finds a value's bin: 0 the library's choice, 1 a count of compares, 2 a search (the same bin) */
+} s4b_spread_in;
+typedef struct {
+  double* mean; double* m2;       /* 4 + 2 T each, independently NULL where not wanted */
+  double* quantiles;              /* n_probs x (4 + 2 T), prob-major; NULL when n_probs = 0 */
+  double* draws;                  /* (4 + 2 T) x num_samples, statistic-major */
+  double weight;                  /* W */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did, in s4b_groups_out.info's layout: [0] route of the value kernel (as s4b_contrast_out.info[0]), [1] rows per chunk, [2] chunks,
+   * [3] kernel launches (per chunk: values, k_spread_reduce, k_spread_fold; then k_spread_finish, + k_level_rows with mean or m2, + the sort with
+   * probs), [4] bytes of device memory the call allocated, [5] pooled draws, [6] T, [7] slabs whose weight is 0 */
+  int64_t info[8];
+} s4b_spread_out;
+int S4B_FN(predict_spread)(s4b_sampler* s, const s4b_spread_in* in, s4b_spread_out* out);
+
 /* extension (R: quantiles and scores of extract(fit, "ppd") against held-out responses, formed on the device): the POSTERIOR PREDICTIVE read-out per row
  * over the draws of `s` and its peers, pooled as predict_quantiles pools them: prediction intervals for NEW OBSERVATIONS and the scores of held-out
  * responses y, without the rows-times-draws matrix.  Row i is a row of the call; k is the pooled draw index (the draws of `s`, then the peers' in peer

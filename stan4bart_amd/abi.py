@@ -143,6 +143,15 @@ class ProjectionOut(C.Structure):      # s4b_projection_out
                 ("weight", C.c_double), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
 
 
+class SpreadIn(C.Structure):           # s4b_spread_in
+    _fields_ = [("arms", ContrastIn), ("n_arms", C.c_int32), ("n_thresholds", C.c_int32), ("thresholds", c_double_p), ("bin_index", C.c_int32)]
+
+
+class SpreadOut(C.Structure):          # s4b_spread_out
+    _fields_ = [("mean", c_double_p), ("m2", c_double_p), ("quantiles", c_double_p), ("draws", c_double_p), ("weight", C.c_double),
+                ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
 class PpdIn(C.Structure):              # s4b_ppd_in
     _fields_ = [("rows", SummaryIn), ("y", c_double_p), ("sigma", c_double_p), ("row_scale", c_double_p), ("noise_key", C.c_uint64),
                 ("n_probs", C.c_int32), ("probs", c_double_p), ("n_peers", C.c_int32), ("peers", C.POINTER(C.c_void_p)),
@@ -188,6 +197,10 @@ GROUPS_LEVEL_BYTES_MAX = 1 << 30       # S4B_GROUPS_LEVEL_BYTES_MAX: the level m
 PROJECTION_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "deficient", "columns")
 PROJECTION_COLUMNS_MAX = 32            # S4B_PROJECTION_COLUMNS_MAX: design columns of one s4b_predict_projection call at most
 PROJECTION_SLAB = 128                  # S4B_PROJECTION_SLAB: rows per slab of the moments' fold
+SPREAD_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "thresholds", "zero_slabs")
+SPREAD_THRESHOLDS_MAX = 64             # S4B_SPREAD_THRESHOLDS_MAX: thresholds of one s4b_predict_spread call at most
+SPREAD_SLAB = 128                      # S4B_SPREAD_SLAB: rows per slab of the moments' and the bins' fold
+SPREAD_BIN_INDEX = {"auto": 0, "compare": 1, "search": 2}
 PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
 LOO_INFO = QUANTILE_INFO               # (s4b_loo_out.info likewise; rows_per_sort: rows per workgroup of k_loo_rows)
 LOO_OUTPUTS = ("elpd_loo", "pareto_k", "lpd", "ess")
@@ -439,6 +452,7 @@ class Sampler:
             "predict_contrast": [vp, C.POINTER(ContrastIn), C.POINTER(ContrastOut)],
             "predict_groups": [vp, C.POINTER(GroupsIn), C.POINTER(GroupsOut)],
             "predict_projection": [vp, C.POINTER(ProjectionIn), C.POINTER(ProjectionOut)],
+            "predict_spread": [vp, C.POINTER(SpreadIn), C.POINTER(SpreadOut)],
             "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
             "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
             "predict_convergence": [vp, C.POINTER(ConvIn), C.POINTER(ConvOut)],
@@ -1111,6 +1125,73 @@ class Sampler:
         return dict(res, weight=float(out.weight), scale=scale, deficient=int(out.info[6]), draws_pooled=int(out.num_samples),
                     info=dict(self.projection_info))
 
+    def spread_draws(self) -> int:
+        """The kept draws of this sampler, as ``s4b_predict_spread``'s query form reports them."""
+        probe = SpreadOut()
+        self._check(self._f("predict_spread")(self._h, None, C.byref(probe)))
+        return int(probe.num_samples)
+
+    @staticmethod
+    def spread_names(n_thresholds: int):
+        """The statistics of ``s4b_predict_spread``'s matrix in row order: 4 + 2 T names."""
+        T = int(n_thresholds)
+        return ["mean", "sd", "min", "max"] + [f"share_above[{j}]" for j in range(T)] + [f"part_above[{j}]" for j in range(T)]
+
+    def predict_spread(self, x_test: np.ndarray, thresholds=(), x_test0=None, n_arms: int = 1, probs=(), peers=(), peer_dense_coef=None,
+                       peer_ell_coef=None, offset=None, offset0=None, dense=None, dense0=None, dense_coef=None, ell_index=None, ell_index0=None,
+                       ell_value=None, ell_value0=None, ell_coef=None, link: int = 0, weights=None, outputs=("mean", "m2", "draws"), route="auto",
+                       stage_nodes: int = 0, scratch_bytes: int = 0, bin_index="auto") -> dict:
+        """``s4b_predict_spread``: per pooled draw the spread of the rows' values ACROSS THE ROWS — ``n_arms`` 1: ``predict_quantiles``' value, 2:
+        ``predict_contrast``'s d, the arms given as there: the weighted mean, the standard deviation (population form), the smallest and the largest
+        value among the rows with weight, and for each of the T <= 64 strictly ascending ``thresholds`` (+-inf allowed) the share of the weight on
+        the rows strictly above it and the part of the mean those rows contribute; over the draws the mean, m2 and the ``probs`` quantiles of each
+        of these 4 + 2 T statistics.  ``weights`` None (1) or [rows], non-negative, not all 0.  ``outputs``: any of "mean", "m2", "draws" (the
+        [(4 + 2 T) x pooled draws] matrix itself).  ``bin_index`` "auto", "compare" or "search": how the kernel finds a value's bin (the same
+        result).  Returns names, mean, m2 [4 + 2 T], quantiles [Q x (4 + 2 T)] or None, draws or None, weight, thresholds, ``draws_pooled`` and
+        info: SPREAD_INFO."""
+        fn = getattr(self._lib, self._pfx + "predict_spread", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_spread")
+
+        def draws(smp):
+            probe = SpreadOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        unknown = set(outputs) - {"mean", "m2", "draws"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        th = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+        if th.ndim != 1:
+            raise ValueError(f"thresholds must be a vector, not shape {th.shape}")
+        if isinstance(bin_index, str) and bin_index not in SPREAD_BIN_INDEX:
+            raise ValueError(f"bin_index must be one of {', '.join(SPREAD_BIN_INDEX)}, not {bin_index!r}")
+        n = np.shape(x_test)[0]
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.shape != (n,):
+                raise ValueError(f"weights must be [{n}], not shape {weights.shape}")
+        w = None if weights is None else weights[None, :]
+        arms, keep, rows, _, S, pr = self._contrast_in(draws, x_test, x_test0, probs, peers, peer_dense_coef, peer_ell_coef, offset, offset0, dense, dense0,
+                                                       dense_coef, ell_index, ell_index0, ell_value, ell_value0, ell_coef, link, w, route, stage_nodes,
+                                                       scratch_bytes)
+        T = len(th)
+        M = 4 + 2 * min(T, SPREAD_THRESHOLDS_MAX)          # (more thresholds are refused by the library: no array is sized by them)
+        res = dict(mean=np.zeros(M) if "mean" in outputs else None, m2=np.zeros(M) if "m2" in outputs else None,
+                   quantiles=np.zeros((len(pr), M)) if len(pr) else None, draws=np.zeros((M, S)) if "draws" in outputs else None)
+        spare = np.zeros(M)          # (nothing asked for: the library needs a pointer to tell the call from a query)
+        arg = SpreadIn(arms=arms, n_arms=int(n_arms), n_thresholds=T, thresholds=_dp(th) if T else None,
+                       bin_index=int(SPREAD_BIN_INDEX.get(bin_index, bin_index)))
+        out = SpreadOut(mean=_dp(res["mean"]), m2=_dp(res["m2"]), quantiles=_dp(res["quantiles"]), draws=_dp(res["draws"]))
+        if all(v is None for v in res.values()):
+            out.mean = _dp(spare)
+        self.spread_info = dict(zip(SPREAD_INFO, [0] * 8))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        self.spread_info = dict(zip(SPREAD_INFO, (int(v) for v in out.info)))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep, spare
+        return dict(res, names=self.spread_names(T), weight=float(out.weight), thresholds=th, draws_pooled=int(out.num_samples),
+                    info=dict(self.spread_info))
+
     def predict_ppd(self, x_test: np.ndarray, probs=(), y=None, sigma=None, row_scale=None, noise_key: int = 0, peers=(), peer_sigma=None,
                     peer_dense_coef=None, peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None, ell_coef=None,
                     link: int = 0, lpd: bool = True, moments: bool = True, pit: Optional[bool] = None, route="auto", stage_nodes: int = 0,
@@ -1405,6 +1486,9 @@ class StoredSampler:
     column_scales = staticmethod(Sampler.column_scales)
     projection_draws = Sampler.projection_draws
     predict_projection = Sampler.predict_projection
+    spread_draws = Sampler.spread_draws
+    spread_names = staticmethod(Sampler.spread_names)
+    predict_spread = Sampler.predict_spread
     predict_ppd = Sampler.predict_ppd
     predict_loo = Sampler.predict_loo
     predict_convergence = Sampler.predict_convergence

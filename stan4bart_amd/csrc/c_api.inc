@@ -103,6 +103,14 @@ int S4B_FN(predict_projection)(s4b_sampler* s, const s4b_projection_in* in, s4b_
   s->core.predict_projection(in, out, peers.empty() ? nullptr : peers.data());
   S4B_CATCH
 }
+int S4B_FN(predict_spread)(s4b_sampler* s, const s4b_spread_in* in, s4b_spread_out* out) {
+  S4B_NEED(s, "predict_spread") S4B_TRY
+  s->core.dev().bind();
+  std::vector<const s4b::SamplerCore<S4B_DEV>*> peers;          // (a NULL handle stays NULL: the core refuses it by its position)
+  if (in && out && in->arms.n_peers > 0 && in->arms.peers) for (int x = 0; x < in->arms.n_peers; ++x) peers.push_back(in->arms.peers[x] ? &in->arms.peers[x]->core : nullptr);
+  s->core.predict_spread(in, out, peers.empty() ? nullptr : peers.data());
+  S4B_CATCH
+}
 int S4B_FN(predict_ppd)(s4b_sampler* s, const s4b_ppd_in* in, s4b_ppd_out* out) {
   S4B_NEED(s, "predict_ppd") S4B_TRY
   s->core.dev().bind();

@@ -1634,6 +1634,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 #include "dev_contrast.inc"
 #include "dev_groups.inc"
 #include "readout_projection.inc"
+#include "readout_spread.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
 static void use_device(int device) {
@@ -2747,6 +2748,8 @@ class DevHip {
   void predict_groups(const GroupsCall& c) { groups_run(stream_, a_.P, c, launches_); }
   // s4b_predict_projection (readout_projection.inc), likewise
   void predict_projection(const ProjectionCall& c) { projection_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_spread (readout_spread.inc), likewise
+  void predict_spread(const SpreadCall& c) { spread_run(stream_, a_.P, c, launches_); }
   // s4b_predict_ppd (dev_ppd.inc), likewise
   void predict_ppd(const PpdCall& c) { ppd_run(stream_, a_.P, c, launches_); }
   // s4b_predict_loo (dev_loo.inc), likewise

@@ -141,6 +141,18 @@ struct ProjectionCall {
   double* mean; double* m2; double* quantiles; double* pAbove;          // [K + 1], [K + 1], [Q x (K + 1)], [K + 1]: the coefficients, then r2
 };
 
+// does the device layer form the across-row spread of the rows' values per pooled draw (s4b_predict_spread)?  As has_predict_groups.
+template <class D, class = void> struct has_predict_spread : std::false_type {};
+template <class D> struct has_predict_spread<D, std::void_t<decltype(&D::predict_spread)>> : std::true_type {};
+// one s4b_predict_spread call as the device layer sees it: the arms as GroupsCall's, the validated thresholds [T] ascending, the row weights (NULL:
+// 1), W > 0 and the slabs without weight as the host formed them, every output NULL where it was not asked for
+struct SpreadCall {
+  ContrastCall arms;
+  int nArms; const double* thresholds; int T, binIndex;
+  const double* rowWeights; double W; int64_t zeroSlabs;
+  double* mean; double* m2; double* quantiles; double* draws;          // [4 + 2 T], [4 + 2 T], [Q x (4 + 2 T)], [(4 + 2 T) x S]
+};
+
 // does the device layer form the posterior predictive read-out over the pooled kept draws (s4b_predict_ppd)?  As has_predict_quantiles.
 template <class D, class = void> struct has_predict_ppd : std::false_type {};
 template <class D> struct has_predict_ppd<D, std::void_t<decltype(&D::predict_ppd)>> : std::true_type {};
@@ -897,6 +909,58 @@ class SamplerCore {
       out->num_samples = S;
       return S;
     } else throw std::invalid_argument("predict_projection: this device layer has no projection kernels (the per-draw least squares is formed by the HIP library only)");
+  }
+  // s4b_predict_spread: per pooled draw the weighted mean, standard deviation and extremes of the rows' values ACROSS THE ROWS — one arm:
+  // predict_quantiles' value, two arms: predict_contrast's d — and the share of the weight, and the part of the mean, above each of up to 64
+  // thresholds; of those series the mean, m2 and type-7 quantiles over the draws.  W and the slabs without weight are formed here, in row order.
+  // Everything is validated here, before any launch.
+  int64_t predict_spread(const s4b_spread_in* in, s4b_spread_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_spread: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    out->weight = 0.0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in || (!out->mean && !out->m2 && !out->quantiles && !out->draws)) return own;          // query
+    if constexpr (has_predict_spread<Dev>::value) {
+      const std::string who = "predict_spread";
+      const s4b_contrast_in* ar = &in->arms;
+      const s4b_summary_in* rw = &ar->rows;
+      const int T = in->n_thresholds;
+      if (T < 0 || T > S4B_SPREAD_THRESHOLDS_MAX)
+        throw std::invalid_argument(who + ": n_thresholds must lie in [0, " + std::to_string(S4B_SPREAD_THRESHOLDS_MAX) + "], not " + std::to_string(T));
+      if (T > 0 && !in->thresholds) throw std::invalid_argument(who + ": NULL thresholds");
+      for (int j = 0; j < T; ++j) {
+        if (std::isnan(in->thresholds[j])) throw std::invalid_argument(who + ": threshold " + std::to_string(j) + " is a NaN");
+        if (j > 0 && !(in->thresholds[j] > in->thresholds[j - 1])) throw std::invalid_argument(who + ": the thresholds are not strictly ascending at index " + std::to_string(j));
+      }
+      if (in->n_arms != 1 && in->n_arms != 2) throw std::invalid_argument(who + ": n_arms must be 1 (the fitted value) or 2 (the contrast), not " + std::to_string(in->n_arms));
+      if (in->bin_index < 0 || in->bin_index > 2) throw std::invalid_argument(who + ": bin_index must be 0 (the library's choice), 1 (compares) or 2 (search), not " + std::to_string(in->bin_index));
+      contrast_check_in(who, ar, 1);
+      if (in->n_arms == 1 && (ar->x_test0 || ar->offset0 || ar->dense0 || ar->ell_index0 || ar->ell_value0))
+        throw std::invalid_argument(who + ": n_arms = 1 takes no arm-0 pointer (x_test0, offset0, dense0, ell_index0, ell_value0 must be NULL)");
+      if (ar->n_probs > 0 && !out->quantiles) throw std::invalid_argument(who + ": n_probs > 0 needs quantiles");
+      const int64_t nT = rw->n_test;
+      double W = 0.0, Ws = 0.0;          // in row order, in double: part of the definition
+      int64_t zeroSlabs = 0;
+      for (int64_t i = 0; i < nT; ++i) {
+        const double w = rw->n_weights ? rw->weights[i] : 1.0;
+        if (!(w >= 0.0) || std::isinf(w)) throw std::invalid_argument(who + ": weight " + std::to_string(w) + " of row " + std::to_string(i) + " is negative or not finite");
+        W += w; Ws += w;
+        if ((i + 1) % S4B_SPREAD_SLAB == 0 || i + 1 == nT) { zeroSlabs += Ws == 0.0; Ws = 0.0; }
+      }
+      if (!(W > 0.0)) throw std::invalid_argument(who + ": the weights sum to 0 (no row carries weight)");
+      SpreadCall g{};
+      ArmsHold hold;
+      const int64_t S = contrast_arms(who, ar, peers, in->n_arms == 2, nullptr, g.arms, hold);
+      out->weight = W;
+      g.arms.rows.info = out->info; g.arms.rows.G = 0; g.arms.rows.weights = nullptr;
+      g.nArms = in->n_arms; g.thresholds = in->thresholds; g.T = T; g.binIndex = in->bin_index;
+      g.rowWeights = rw->n_weights ? rw->weights : nullptr; g.W = W; g.zeroSlabs = zeroSlabs;
+      g.mean = out->mean; g.m2 = out->m2; g.quantiles = ar->n_probs > 0 ? out->quantiles : nullptr; g.draws = out->draws;
+      dev_.predict_spread(g);
+      out->num_samples = S;
+      return S;
+    } else throw std::invalid_argument("predict_spread: this device layer has no spread kernels (the across-row read-out is formed by the HIP library only)");
   }
   // s4b_predict_ppd: the posterior predictive distribution of new observations at the rows — type-7 quantiles of y_rep = z + sigma row_scale e — and the
   // scores of held-out responses y (log predictive density, mean and squared deviations of the pointwise log-likelihood, PIT), per row over the

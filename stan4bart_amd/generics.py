@@ -16,7 +16,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from .abi import GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, PROJECTION_COLUMNS_MAX, Sampler
+from .abi import GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, PROJECTION_COLUMNS_MAX, SPREAD_THRESHOLDS_MAX, Sampler
 from .fit import GroupTerm, chain_seeds, hip_sampler_factory, make_sampler_args, make_z_csr, qr_back_transform
 from .rcompat import RRng
 
@@ -790,6 +790,112 @@ class Stan4bartFit:
         return {"names": names, "coef": r["coef"], "mean": r["mean"][:K], "sd": sd, "probs": pr, "quantiles": q[:, :K],
                 "p_above": None if r["p_above"] is None else r["p_above"][:K], "r2": r["r2"], "r2_mean": float(r["mean"][K]), "r2_quantiles": q[:, K],
                 "center": shift, "weight": r["weight"], "deficient": r["deficient"], "draws": S, "info": r["info"]}
+
+    # ------------------------------------------------------------------ predict_spread
+    def predict_spread(self, x_bart=None, x_bart0=None, X=None, X0=None, groups: Optional[Sequence[GroupTerm]] = None,
+                       groups0: Optional[Sequence[GroupTerm]] = None, offset=None, offset0=None, treatment=None, levels=(1.0, 0.0),
+                       thresholds=(0.0,), row_weights=None, probs=(0.025, 0.5, 0.975), return_draws: bool = False, type: str = "ev",
+                       sample_new_levels: bool = True, seed: Optional[int] = None):
+        """Effect heterogeneity: how the rows' values are spread ACROSS THE ROWS within a posterior draw, and the posterior of that spread.  Any
+        arm-0 argument (suffix 0) or ``treatment`` makes the values the contrast of two arms as ``predict_contrast`` forms it, otherwise the one
+        arm's expected value as ``predict_quantiles`` forms it.  Per draw, on the device without a [rows x draws] matrix and in ONE pooled call
+        (``s4b_predict_spread``: the first chain's sampler with the others as its peers): the weighted mean, the standard deviation over the rows
+        (population form), the smallest and largest value, and for each of the up to 64 strictly ascending ``thresholds`` the share of the weight
+        on the rows strictly above it and the part of the mean those rows contribute.  ``row_weights`` None (1) or [rows], non-negative, not all 0.
+        Returns ``names`` (the 4 + 2 T statistics), per statistic ``mean``, ``sd`` (over the draws, ddof 1) and ``quantiles`` [Q, statistics],
+        ``probs``, ``weight``, ``thresholds``, ``draws`` (the pooled count), ``info`` and the named views ``effect_sd``, ``share_above`` [T],
+        ``part_above`` [T], ``mean_above`` [T] (part / share: the mean value among the rows above) and ``gain`` [T] (part - threshold x share: the
+        gain of treating exactly the rows above at that cost), the last two NaN in a draw whose share is 0.  With ``return_draws`` a view is its
+        draw vector ([draws] or [T, draws], chain after chain) and ``matrix`` [statistics, draws] is returned too; otherwise a view is the dict of
+        its ``mean``, ``sd`` and ``quantiles`` over the draws."""
+        if type == "ppd":
+            raise ValueError("predict_spread does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("predict_spread requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_spread needs x_bart, the new rows of the BART predictors")
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or len(pr) > 16 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of at most 16 values in [0, 1], not {probs!r}")
+        th = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        if th.ndim != 1 or len(th) > SPREAD_THRESHOLDS_MAX:
+            raise ValueError(f"'thresholds' must be a vector of at most {SPREAD_THRESHOLDS_MAX} values, not {len(th) if th.ndim == 1 else th.shape}")
+        if np.any(np.isnan(th)):
+            raise ValueError("'thresholds' holds a NaN")
+        if not np.all(th[1:] > th[:-1]):
+            raise ValueError("'thresholds' must be strictly ascending")
+        rows = np.shape(x_bart)[0]
+        w = None
+        if row_weights is not None:
+            w = np.asarray(row_weights, dtype=np.float64)
+            if w.shape != (rows,) or not np.all(np.isfinite(w)) or np.any(w < 0.0):
+                raise ValueError(f"row_weights must be [{rows}] finite non-negative values")
+            if not w.sum() > 0.0:
+                raise ValueError("row_weights sum to 0: no row carries weight")
+        two = treatment is not None or any(a is not None for a in (x_bart0, X0, groups0, offset0))
+        x_bart, x_bart0, kw, peer_kw = self._contrast_arms(x_bart, x_bart0, X, X0, groups, groups0, offset, offset0, treatment, levels, type,
+                                                           sample_new_levels, seed)
+        r = self.samplers[0].predict_spread(x_test=x_bart, thresholds=th, x_test0=x_bart0, n_arms=2 if two else 1, probs=pr, weights=w,
+                                            outputs=("mean", "m2", "draws"), **peer_kw, **kw)
+        S, T, D = r["draws_pooled"], len(th), r["draws"]
+        M = 4 + 2 * T
+        sd = np.sqrt(r["m2"] / (S - 1)) if S > 1 else np.full(M, np.nan)
+        q = r["quantiles"] if r["quantiles"] is not None else np.zeros((0, M))
+        share, part = D[4:4 + T], D[4 + T:]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            none = share == 0.0
+            mean_above = np.where(none, np.nan, part / share)
+            gain = np.where(none, np.nan, part - th[:, None] * share)
+
+        def view(rows_of, derived=None):
+            """A named view: the draws, or the summary over them (the device's for a statistic of the matrix, numpy's for a derived one)."""
+            if return_draws:
+                return D[rows_of] if derived is None else derived
+            if derived is None:
+                return {"mean": r["mean"][rows_of], "sd": sd[rows_of], "quantiles": q[:, rows_of]}
+            with np.errstate(invalid="ignore"):
+                return {"mean": derived.mean(axis=1), "sd": derived.std(axis=1, ddof=1) if S > 1 else np.full(len(derived), np.nan),
+                        "quantiles": np.quantile(derived, pr, axis=1) if len(pr) else np.zeros((0, len(derived)))}
+        res = {"names": r["names"], "mean": r["mean"], "sd": sd, "probs": pr, "quantiles": q, "weight": r["weight"], "thresholds": th, "draws": S,
+               "info": r["info"], "effect_sd": view(1), "share_above": view(slice(4, 4 + T)), "part_above": view(slice(4 + T, M)),
+               "mean_above": view(None, mean_above), "gain": view(None, gain)}
+        if return_draws:
+            res["matrix"] = D
+        return res
+
+    def bayes_R2(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, probs=(0.025, 0.5, 0.975),
+                 sample_new_levels: bool = True, seed: Optional[int] = None):
+        """The Bayes R-squared of Gelman, Goodrich, Gabry and Vehtari (rstanarm's ``bayes_R2``) at the given rows, for a continuous response: per
+        posterior draw ``R2 = v / (v + sigma^2)`` with ``v`` the variance of the fitted values across the rows (R's ``var``: n - 1 in the
+        denominator) and ``sigma`` the draw's residual standard deviation.  The variance comes from ONE ``predict_spread`` call with one arm, so
+        no [rows x draws] matrix is formed.  Returns ``r2`` [draws] (chain after chain), ``mean``, ``median``, ``probs`` and ``quantiles``."""
+        if self.family == "binomial":
+            raise ValueError("bayes_R2 is defined here for a continuous response only: a binary fit has no residual standard deviation")
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of values in [0, 1], not {probs!r}")
+        if x_bart is None:
+            raise ValueError("bayes_R2 needs x_bart, the rows of the BART predictors")
+        n = np.shape(x_bart)[0]
+        if n < 2:
+            raise ValueError("bayes_R2 needs at least two rows")
+        s = self.predict_spread(x_bart=x_bart, X=X, groups=groups, offset=offset, thresholds=(), probs=(), return_draws=True, type="ev",
+                                sample_new_levels=sample_new_levels, seed=seed)
+        sig = self.stan[self.par_names.index("aux.1")]               # [iter, chain]; pooled draw k is draw k % iter of chain k // iter
+        r2 = self.r2_from_spread(s["effect_sd"], sig.T.reshape(-1), n)
+        return {"r2": r2, "mean": float(r2.mean()), "median": float(np.median(r2)), "probs": pr, "quantiles": np.quantile(r2, pr) if len(pr) else np.zeros(0)}
+
+    @staticmethod
+    def r2_from_spread(sd_rows, sigma, n: int):
+        """``v / (v + sigma^2)`` per draw, ``v = sd_rows^2 n / (n - 1)``: the population-form standard deviation across the ``n`` rows, as
+        ``predict_spread`` returns it, turned into R's ``var``."""
+        sd_rows, sigma = np.asarray(sd_rows, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
+        if sd_rows.shape != sigma.shape:
+            raise ValueError(f"{sd_rows.shape[0] if sd_rows.ndim else 1} draws of the spread, but {sigma.shape[0] if sigma.ndim else 1} of sigma")
+        v = sd_rows * sd_rows * (float(n) / float(n - 1))
+        return v / (v + sigma * sigma)
 
     # ------------------------------------------------------------------ predict_ppd
     def predict_ppd(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, y=None, probs=(0.025, 0.5, 0.975),
