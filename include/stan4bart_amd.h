@@ -855,6 +855,23 @@ int S4B_FN(test_draw_latents)(s4b_sampler* s);
  * answering from the last transition).  Refused on a stored sampler, for non-finite coefficients and for a sigma that is not positive. */
 int S4B_FN(test_hand_off)(s4b_sampler* s, const double* beta, const double* b, double sigma, int32_t update_scale);
 
+/* TEST ENTRY (no reference counterpart): ONE evaluation of the Stan block's O(N) sums (ss = e'We, X'We, Z'We) from the state as it stands, through the
+ * members run() itself uses, and nothing else.  mode -1: the evaluation of one leapfrog of hmc_mode 1 — e = e0 - X beta - Z b with the e0 the last
+ * evaluation of the other kind left on the device; beta (K) and b (q) may hold non-finite values (ordinary arithmetic: the evaluation is then
+ * rejected by the device's flag and repeated in plain doubles).  mode 0..3: the evaluation of one Gibbs iteration with that Stan-offset mode
+ * (0: e = y; 1: y - fit; 2: y - user offset; 3: y - fit - user offset; 2 and 3 are refused without a user offset); beta and b are ignored; e0 is
+ * rewritten on the device as run() rewrites it, nothing else of the chain moves.  set_exp: NULL (the power-of-two scales of the fixed-point sums are
+ * what the history left them) or three binary exponents in [-900, 900] for |e|^2, X'e, Z'e that replace them before the launch; the memory of
+ * consecutive failures is cleared with them, so {0, 0, 0} is what run() and set_state start from.  sums[1 + K + q]: ss, X'e, Z'e as the sampler would
+ * have used them (after a rejected fixed-point evaluation: the plain-double values).  info[S4B_STAN_SUMS_INFO]: [0] 1 = the fixed-point result was
+ * accepted; [1] why not, a sum of 1 = the device's flag (something non-finite or of 2^42 and more after scaling), 2 = a magnitude word of 2^32 and
+ * more, 4 = an exponent word below 4 (resolution); [2..4] the exponents of this launch; [5..7] the exponents after it; [8..10] the magnitude words;
+ * [11..13] the exponent words as the device wrote them (0: nothing but zeros went in, else 4000 + the binary exponent of the largest workgroup
+ * magnitude); [14] workgroups of the launch; [15] 1 = this shape has the fixed-point path at all; [16], [17] the counters of s4b_get_fused_stats.
+ * A shape without that path (K > 16 or q > 4096) and the emulated device layer evaluate in plain doubles: info is all 0.  Refused on a stored sampler. */
+#define S4B_STAN_SUMS_INFO 18
+int S4B_FN(test_stan_sums)(s4b_sampler* s, int32_t mode, const double* beta, const double* b, const int32_t* set_exp, double* sums, int64_t* info);
+
 /* finalizer of the externalptr — src/init.cpp:1152-1165 */
 void S4B_FN(free)(s4b_sampler* s);
 

@@ -418,6 +418,7 @@ class Sampler:
         self._check(self._f("get_dims")(self._h, dims))
         self.num_pars, self.n, self.n_test, self.p, self.n_trees = (int(d) for d in dims)
         self.keep_fits = bool(a.keep_fits)
+        self.K, self.q = int(K), int(q)
         self.callback_results: list = []
         self._pending_exc = None
 
@@ -457,6 +458,7 @@ class Sampler:
             "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
             "predict_convergence": [vp, C.POINTER(ConvIn), C.POINTER(ConvOut)],
             "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
+            "test_stan_sums": [vp, i32, dp, dp, ip, dp, C.POINTER(i64)],
         }
         for name, argtypes in sig.items():
             fn = getattr(self._lib, self._pfx + name, None)
@@ -701,6 +703,27 @@ class Sampler:
         offset type, sigma, the rescaling with or without a new response scale) and nothing else; Stan's position and both generators stay."""
         beta, b = _f64(np.atleast_1d(beta)), _f64(np.atleast_1d(b))
         self._check(self._f("test_hand_off")(self._h, _dp(beta) if beta.size else None, _dp(b) if b.size else None, float(sigma), int(bool(update_scale))))
+
+    STAN_SUMS_INFO = 18
+
+    def test_stan_sums(self, mode: int, beta=None, b=None, set_exp=None):
+        """TEST ENTRY (include/stan4bart_amd.h): one evaluation of the Stan block's O(N) sums.  ``mode`` -1: one leapfrog's evaluation with ``beta``,
+        ``b`` (non-finite values allowed); 0..3: one Gibbs iteration's evaluation with that Stan-offset mode.  ``set_exp``: None or the three binary
+        exponents of the fixed-point scales for this launch.  Returns (sums [1 + K + q]: ss, X'e, Z'e; info: dict of what the host's checks saw)."""
+        K, q = self.K, self.q
+        beta = _f64(np.zeros(K) if beta is None else np.atleast_1d(beta))
+        b = _f64(np.zeros(q) if b is None else np.atleast_1d(b))
+        if beta.size != K or b.size != q:
+            raise ValueError(f"test_stan_sums: beta needs {K} entries and b {q}")
+        ex = None if set_exp is None else np.ascontiguousarray(set_exp, dtype=np.int32)
+        if ex is not None and ex.shape != (3,):
+            raise ValueError("test_stan_sums: set_exp holds three exponents")
+        sums = np.zeros(1 + K + q)
+        info = (C.c_int64 * Sampler.STAN_SUMS_INFO)()
+        self._check(self._f("test_stan_sums")(self._h, int(mode), _dp(beta) if K else None, _dp(b) if q else None, _ip(ex) if ex is not None else None, _dp(sums), info))
+        v = [int(x) for x in info]
+        return sums, dict(accepted=bool(v[0]), reject=v[1], exp_used=tuple(v[2:5]), exp_after=tuple(v[5:8]), mag=tuple(v[8:11]), exw=tuple(v[11:14]),
+                          grid=v[14], fused=bool(v[15]), evals=v[16], fallbacks=v[17])
 
     def get_sweep_busy(self) -> int:
         """Persistent launches that found the device shared (roll call failed; their sweeps ran as k_step launches) since creation."""

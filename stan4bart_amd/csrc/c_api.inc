@@ -166,6 +166,9 @@ int S4B_FN(test_draw_latents)(s4b_sampler* s) { S4B_NEED(s, "test_draw_latents")
 int S4B_FN(test_hand_off)(s4b_sampler* s, const double* beta, const double* b, double sigma, int32_t update_scale) {
   S4B_NEED(s, "test_hand_off") S4B_TRY s->core.dev().bind(); s->core.test_hand_off(beta, b, sigma, update_scale != 0); S4B_CATCH
 }
+int S4B_FN(test_stan_sums)(s4b_sampler* s, int32_t mode, const double* beta, const double* b, const int32_t* set_exp, double* sums, int64_t* info) {
+  S4B_NEED(s, "test_stan_sums") S4B_TRY s->core.dev().bind(); s->core.test_stan_sums(mode, beta, b, set_exp, sums, info); S4B_CATCH
+}
 int S4B_FN(get_sweep_busy)(s4b_sampler* s, int64_t* out) { S4B_NEED(s, "get_sweep_busy") S4B_TRY if (!out) throw std::invalid_argument("get_sweep_busy: NULL output pointer"); *out = s->core.dev().sweep_busy(); S4B_CATCH }
 int S4B_FN(get_counters)(s4b_sampler* s, int64_t out[3]) { S4B_NEED(s, "get_counters") S4B_TRY s->core.dev().bind(); s->core.counters(out); S4B_CATCH }
 int S4B_FN(get_nuts_stats)(s4b_sampler* s, double out[4]) { S4B_NEED(s, "get_nuts_stats") S4B_TRY s->core.dev().bind(); s->core.nuts_stats(out); S4B_CATCH }

@@ -2805,6 +2805,7 @@ class DevHip {
     f.parInline = (direct && K_ + q_ <= S_PAR_INLINE && inlineBeta_) ? 1 : 0; f.pad = 0;
     if (f.parInline) { for (int k = 0; k < K_; ++k) f.par[k] = inlineBeta_[k]; for (int j = 0; j < q_; ++j) f.par[K_ + j] = inlineB_[j]; }
     const int grid = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (n_ + SBLOCK - 1) / SBLOCK));
+    fxSeen_.grid = grid;
     if (K_ <= 2) launch_stan_fused_k<2>(f, direct, fusedLds_, grid);
     else if (K_ <= 4) launch_stan_fused_k<4>(f, direct, fusedLds_, grid);
     else if (K_ <= 8) launch_stan_fused_k<8>(f, direct, fusedLds_, grid);
@@ -2831,25 +2832,29 @@ class DevHip {
       if (*flag != (unsigned long long)fusedSeq_) throw std::runtime_error("fused Stan sums: the result hand-off did not arrive");
     }
     fusedParity_ ^= 1;
-    bool bad = (*(const int32_t*)(pinnedAcc_ + W)) != 0;
+    // why the evaluation is rejected, if it is: 1 the device's flag, 2 a magnitude word, 4 the resolution (s4b_test_stan_sums reports these bits)
+    int why = (*(const int32_t*)(pinnedAcc_ + W)) != 0 ? 1 : 0;
     // the magnitudes: sums of absolute contributions in units of 2^10 (after scaling); below 2^32 no limb can have wrapped
     unsigned long long mag[3] = {0, 0, 0};
     for (int g = 0; g < 3; ++g) mag[g] = pinnedAcc_[2 * M + g];
-    for (int g = 0; g < 3; ++g) if (mag[g] >= (1ull << 32)) bad = true;
+    for (int g = 0; g < 3; ++g) if (mag[g] >= (1ull << 32)) why |= 2;
     int ex[3]; bool seen[3];
     for (int g = 0; g < 3; ++g) {
       const unsigned long long m = pinnedAcc_[2 * M + 3 + g];
       seen[g] = m != 0; ex[g] = (int)m - 4000;
-      if (seen[g] && ex[g] < 4) bad = true;         // the scale is far too small for what is being summed now: resolution lost
+      if (seen[g] && ex[g] < 4) why |= 4;           // the scale is far too small for what is being summed now: resolution lost
     }
+    const bool bad = why != 0;
     ++fusedEvals_;
+    for (int g = 0; g < 3; ++g) { fxSeen_.mag[g] = mag[g]; fxSeen_.exw[g] = pinnedAcc_[2 * M + 3 + g]; }
+    fxSeen_.reject = why; fxSeen_.fetched = true;
 #ifdef S4B_FX_DEBUG
     if (bad) fprintf(stderr, "FXDBG eval %lld bad: flag %d mag %llu %llu %llu ex %d %d %d seen %d%d%d exps %d %d %d\n", (long long)fusedEvals_, (int)*(const int32_t*)(pinnedAcc_ + W),
                      mag[0], mag[1], mag[2], ex[0], ex[1], ex[2], (int)seen[0], (int)seen[1], (int)seen[2], fxExp_[0], fxExp_[1], fxExp_[2]);
 #endif
     if (bad) {
       ++fusedFallbacks_;
-      const bool overflow = (*(const int32_t*)(pinnedAcc_ + W)) != 0 || mag[0] >= (1ull << 32) || mag[1] >= (1ull << 32) || mag[2] >= (1ull << 32);
+      const bool overflow = (why & 3) != 0;
       // only the resolution check failed: the exponents are a valid measurement — centre on them, the caller repeats this one in doubles
       if (!overflow) { for (int g = 0; g < 3; ++g) if (seen[g]) fxExp_[g] = std::max(-900, std::min(900, fxExp_[g] + (22 - ex[g]))); fxTinyFail_ = true; }
       else fxTinyFail_ = false;
@@ -2888,6 +2893,20 @@ class DevHip {
     fxLastBad_ = fusedEvals_;
   }
   void fused_stats(int64_t out[2]) const { out[0] = fusedEvals_; out[1] = fusedFallbacks_; }
+  // TEST ENTRY (s4b_test_stan_sums): one evaluation through stan_inputs / leapfrog_sums as run() calls them, with the scales the caller chose (or the
+  // ones history left), and what fetch_fused's checks saw.  sums: [1 + K + q] ss, X'e, Z'e; info: include/stan4bart_amd.h
+  void test_stan_sums(int mode, const double* beta, const double* b, const int32_t* setExp, double* sums, int64_t* info) {
+    if (setExp) { reset_fused_scales(); for (int g = 0; g < 3; ++g) fxExp_[g] = setExp[g]; }
+    for (int i = 0; i < S4B_STAN_SUMS_INFO; ++i) info[i] = 0;
+    const int used[3] = {fxExp_[0], fxExp_[1], fxExp_[2]};
+    fxSeen_ = FxSeen();
+    if (mode < 0) sums[0] = leapfrog_sums(beta, b, sums + 1, sums + 1 + K_);
+    else stan_inputs(mode, false, sums + 1, sums + 1 + K_, sums, nullptr);
+    if (!stanFused_ || !fxSeen_.fetched) return;
+    info[0] = fxSeen_.reject == 0 ? 1 : 0; info[1] = fxSeen_.reject;
+    for (int g = 0; g < 3; ++g) { info[2 + g] = used[g]; info[5 + g] = fxExp_[g]; info[8 + g] = (int64_t)fxSeen_.mag[g]; info[11 + g] = (int64_t)fxSeen_.exw[g]; }
+    info[14] = fxSeen_.grid; info[15] = 1; info[16] = fusedEvals_; info[17] = fusedFallbacks_;
+  }
   // The power-of-two scales of the fixed-point Stan sums follow the evaluation history.  They are put back to their initial values at
   // every run() and set_state(), so that a chain continued in another sampler (get_state / set_state) sums with the same scales as
   // the chain that was never interrupted: bit-identical, not just equal to 2^-67.
@@ -3017,6 +3036,7 @@ class DevHip {
   unsigned long long* fusedAcc_ = nullptr; int32_t* fusedBad_ = nullptr; unsigned long long* pinnedAcc_ = nullptr;
   size_t fusedLds_ = 0; int fusedParity_ = 0; bool stanFused_ = false;
   uint32_t fusedSeq_ = 0; int zFixed_ = -1; const double* inlineBeta_ = nullptr; const double* inlineB_ = nullptr;
+  struct FxSeen { unsigned long long mag[3] = {0, 0, 0}, exw[3] = {0, 0, 0}; int grid = 0, reject = 0; bool fetched = false; } fxSeen_;
   int fxExp_[3] = {0, 0, 0}; int64_t fusedEvals_ = 0, fusedFallbacks_ = 0, fxLastBad_ = -2; bool fxTinyFail_ = false;
   int64_t launches_ = 0;
 };

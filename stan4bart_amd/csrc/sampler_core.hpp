@@ -58,6 +58,9 @@ template <class D> struct has_latent_mode<D, std::void_t<decltype(&D::set_latent
 // does the device layer offer the latent draw on its own (s4b_test_draw_latents)?  A layer without it still builds; the entry is refused there.
 template <class D, class = void> struct has_test_draw_latents : std::false_type {};
 template <class D> struct has_test_draw_latents<D, std::void_t<decltype(&D::test_draw_latents)>> : std::true_type {};
+// does the device layer offer one evaluation of the Stan block's O(N) sums on its own (s4b_test_stan_sums)?  Likewise: refused where it is missing.
+template <class D, class = void> struct has_test_stan_sums : std::false_type {};
+template <class D> struct has_test_stan_sums<D, std::void_t<decltype(&D::test_stan_sums)>> : std::true_type {};
 
 // does the device layer summarise the stored-tree predictions on the device (s4b_predict_summary)?  A layer without it still builds; the entry is refused there.
 template <class D, class = void> struct has_predict_summary : std::false_type {};
@@ -498,6 +501,21 @@ class SamplerCore {
     if (!binary_) { sigma_ = sigma; dev_.set_sigma(sigma_); }
     dev_.rescale(updateScale);
     check_device();
+  }
+
+  // TEST ENTRY (s4b_test_stan_sums): one evaluation of the O(N) sums through the device layer's own stan_inputs / leapfrog_sums, into the caller's
+  // buffers (cX_, cZ_, s0_ — what hmc_mode 0 evaluates from — stay)
+  void test_stan_sums(int mode, const double* beta, const double* b, const int32_t* setExp, double* sums, int64_t* info) {
+    live();
+    if (mode < -1 || mode > 3) throw std::invalid_argument("test_stan_sums: mode must be -1 (one leapfrog's evaluation) or a Stan-offset mode 0..3");
+    if (mode >= 2 && !hasUserOffset_) throw std::invalid_argument("test_stan_sums: modes 2 and 3 subtract the user's offset, this sampler has none");
+    if (!sums || !info) throw std::invalid_argument("test_stan_sums: NULL output pointer");
+    if (mode < 0 && ((K_ > 0 && !beta) || (q_ > 0 && !b))) throw std::invalid_argument("test_stan_sums: NULL coefficients");
+    if (setExp) for (int g = 0; g < 3; ++g) if (setExp[g] < -900 || setExp[g] > 900) throw std::invalid_argument("test_stan_sums: an exponent outside [-900, 900]");
+    // (a model without fixed effects or without grouping terms: the device layer wants the pointers run() hands it, which are never NULL)
+    static const double none = 0.0;
+    if constexpr (has_test_stan_sums<Dev>::value) { dev_.test_stan_sums(mode, beta ? beta : &none, b ? b : &none, setExp, sums, info); check_device(); }
+    else throw std::invalid_argument("test_stan_sums: this device layer has no single evaluation of the Stan sums");
   }
 
   void disengage_adaptation() { live(); nuts_->disengage(); }

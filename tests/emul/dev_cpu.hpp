@@ -321,6 +321,12 @@ class DevCpu {
     }
     return ss;
   }
+  // s4b_test_stan_sums: one evaluation in plain doubles (there is no fixed-point path here: info stays 0)
+  void test_stan_sums(int mode, const double* beta, const double* b, const int32_t*, double* sums, int64_t* info) {
+    for (int i = 0; i < S4B_STAN_SUMS_INFO; ++i) info[i] = 0;
+    if (mode < 0) sums[0] = leapfrog_sums(beta, b, sums + 1, sums + 1 + K_);
+    else stan_inputs(mode, false, sums + 1, sums + 1 + K_, sums, nullptr);
+  }
 
  private:
   void stats(int t) {
