@@ -604,6 +604,90 @@ typedef struct {
 } s4b_ppd_out;
 int S4B_FN(predict_ppd)(s4b_sampler* s, const s4b_ppd_in* in, s4b_ppd_out* out);
 
+/* extension (R: rstanarm's pp_check / bayesplot's ppc_stat over posterior_predict's matrix, formed on the device): POSTERIOR PREDICTIVE CHECKS —
+ * statistics of the replicate y_rep ACROSS THE ROWS within one pooled draw, each to be held against the same statistic of the observed y, summarised
+ * over the draws.  predict_ppd forms y_rep and summarises it along the draws per row; predict_spread reads across the rows, but the expected value.
+ * This call forms the replicate in registers, reduces it across the rows and never stores it.  `rows`, y, sigma, peer_sigma, row_scale, noise_key, the
+ * peers and scratch_bytes are predict_ppd's and follow its rules (rows.n_weights 0; rows.link names the response); y is required.  Row i carries the
+ * weight w_i >= 0 (row_weights, or NULL: every w_i = 1); W = sum_i w_i is the host's sum in row order in double (part of the definition, returned as
+ * `weight`; W == 0 is refused).  thresholds[T], 0 <= T <= S4B_SPREAD_THRESHOLDS_MAX, strictly ascending, +-inf allowed; T must be 0 under link 1.
+ * The replicate, z(i,k) being predict_ppd's z:
+ *   link 0   y_rep(i,k) = z + sd e(i,k), sd = sigma[k] row_scale[i], e predict_ppd's deviate of (noise_key, i, k): THE SAME BITS predict_ppd sorts
+ *            under the same key, so a check and an interval of one key speak of one replicate.
+ *   link 1   y_rep(i,k) = 1 where u(i,k) <= Phi(z), else 0; u the (0, 1] uniform (53 bits) of the FIRST TWO words of the same Philox block
+ *            (counter {i low, i high, k, 0x50504431}); Phi(z) = erfc(-z / sqrt 2) / 2.
+ * Per pooled draw k the matrix D[m, k] of M = 7 + T statistics, x = y_rep:
+ *     m = 0          mean_k = sum_i w_i x / W
+ *     m = 1          sd_k = sqrt(M2_k / W),  M2_k = sum_i w_i (x - mean_k)^2       (population form)
+ *     m = 2          m3_k = M3_k / W,        M3_k = sum_i w_i (x - mean_k)^3       (the skewness is m3 / sd^3: callers form it, NaN where sd = 0)
+ *     m = 3, 4       min_k, max_k over the rows with w_i > 0
+ *     m = 5 + j      share_above[j] = (sum of w_i over the rows with x > t_j) / W    (strict)
+ *     m = 5 + T      disc_rep      m = 6 + T      disc_obs: the realised discrepancy of the replicate and of the observed y under draw k —
+ *                    link 0 (chi^2 of Gelman, Meng and Stern): sum_i w_i e^2 / W  and  sum_i w_i ((y_i - z) / sd)^2 / W;
+ *                    link 1 (the deviance): -2 sum_i w_i log Phi(+-z) / W, the sign + where y_rep (disc_rep) or y_i (disc_obs) is 1, - where it is 0.
+ * The matrix holds no NaN (under link 1 a row WITH weight whose |z| lies beyond about 38 makes the deviance +inf, which is its value).  The posterior predictive p-value of a statistic is the share of draws with D[m, k] >= observed[m], of the discrepancy
+ * the share with disc_rep >= disc_obs (callers form both from D).  Outputs:
+ *   draws[m, k]         D itself, statistic-major: draws[m * S + k] (at most 71 x 16384 doubles); REQUIRED (NULL makes the call a query)
+ *   observed[m]         m < 5 + T: the mean, sd, m3, min, max and share_above of y itself (x = y_i in the formulas above), formed on the host in the
+ *                       same order of additions; or NULL
+ *   mean[m], m2[m]      mean and sum of squared deviations of D[m, .] over the S draws (as predict_spread's); independently NULL
+ *   quantiles[q, m]     R's type 7 quantiles, prob-major: quantiles[q * M + m]
+ *   weight              W
+ * THE ORDER OF THE ADDITIONS is fixed and part of the interface: no floating-point atomics, no data-dependent order.  The rows are cut into slabs
+ * of S4B_SPREAD_SLAB = 128 (a chunk of this call is a multiple of 128 rows), and the deviate belongs to the row of the CALL, so the result does not
+ * depend on scratch_bytes, the route, or live versus stored samplers, bit for bit.
+ *   Moments.  Per slab, with the shift c = the replicate of the slab's first row and d_i = x_i - c: W_s = fold of w_i, s1 = fold of w_i d_i,
+ *   s2 = fold of (w_i d_i) d_i, s3 = fold of ((w_i d_i) d_i) d_i, left folds in row order from +0; a term and its addition may be one fused
+ *   multiply-add.  With d = s1 / W_s the slab's partial is (W_s, mean_s = c + d, M2_s = max(0, s2 - d s1), M3_s = (s3 - 3 d s2) + 2 d^2 s1).  The
+ *   partials combine over the slabs in ascending order by the pairwise update: delta = mean_b - mean_a, W_ab = W_a + W_b,
+ *       M3 = M3_a + M3_b + delta^3 W_a W_b (W_a - W_b) / W_ab^2 + 3 delta (W_a M2_b - W_b M2_a) / W_ab       (Pebay)
+ *       M2 = M2_a + M2_b + delta^2 W_a W_b / W_ab,   mean = mean_a + delta W_b / W_ab                        (Chan, Golub, LeVeque)
+ *   A partial with W_s = 0 is skipped; the first partial with positive weight is taken as it is.  D divides by the host's W.
+ *   Bins.  bin(x) = #{j : x > t_j}.  Per slab and bin cw[b] = fold of w_i in row order from +0; over the slabs added in ascending order; after the
+ *   last chunk above_w[j] = sum_{b > j} cw[b] is added from b = T downward.  Without weights cw are counts: share_above is count / n_test exactly.
+ *   Discrepancies.  Per slab the fold of w_i (e e) and of w_i (r r), r = (y_i - z) / sd (link 0), or of w_i log Phi(+-z) (link 1), in row order
+ *   from +0, a row with w_i = 0 adding no term (so a row without weight never brings 0 x -inf under link 1); over the slabs added in ascending
+ *   order; D holds total / W (link 0), (-2 total) / W (link 1).
+ *   Extremes are order-free.
+ * Multiplying every weight by a power of two changes no output; multiplying sigma by a power of two and dividing row_scale by it changes none; one
+ * row gives mean = min = max and sd = m3 = 0, bit for bit.  bin_index as predict_spread's.
+ * Refused before anything is launched, info left all zero: T outside [0, 64], T > 0 under link 1, a NaN threshold, thresholds that are not strictly
+ * ascending, a negative or non-finite weight, W == 0, bin_index outside {0, 1, 2}, NULL y, and whatever predict_ppd refuses of the rows, probs
+ * (0 .. 16), y, sigma, row_scale and peers.  The limit of 16384 pooled draws and the query form (draws NULL, or in = NULL: num_samples of `s` alone)
+ * are predict_quantiles'.  Device memory: DESIGN.md 5.15 (no term grows with n_test x S beyond a chunk). */
+typedef struct {
+  s4b_summary_in rows;            /* n_weights 0; link: the response, 0 continuous, 1 binary */
+  const double* y;                /* n_test observed responses; required */
+  const double* sigma;            /* one per draw of `s` (link 0) */
+  const double* row_scale;        /* n_test, or NULL: 1 */
+  uint64_t noise_key;
+  const double* row_weights;      /* n_test, or NULL: 1 */
+  int32_t n_thresholds;           /* T; 0 under link 1 */
+  const double* thresholds;       /* T, strictly ascending; NULL with T = 0 */
+  int32_t bin_index;              /* 0 the library's choice, 1 a count of compares, 2 a search (the same bin) */
+  int32_t n_probs;                /* 0 .. 16 */
+  const double* probs;
+  int32_t n_peers;
+  s4b_sampler* const* peers;
+  const double* const* peer_dense_coef;
+  const double* const* peer_ell_coef;
+  const double* const* peer_sigma;        /* [n_peers] vectors (one value per draw of that peer), link 0 */
+  int64_t scratch_bytes;
+} s4b_check_in;
+typedef struct {
+  double* mean; double* m2;       /* 7 + T each, independently NULL where not wanted */
+  double* quantiles;              /* n_probs x (7 + T), prob-major; NULL when n_probs = 0 */
+  double* draws;                  /* (7 + T) x num_samples, statistic-major; required */
+  double* observed;               /* 5 + T, or NULL */
+  double weight;                  /* W */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did, in s4b_spread_out.info's layout: [0] route of the value kernel (1 LDS-staged, 2 global), [1] rows per chunk, [2] chunks,
+   * [3] kernel launches (per chunk: values, k_check_reduce, k_check_fold; then k_check_finish, + k_level_rows with mean or m2, + the sort with
+   * probs), [4] bytes of device memory the call allocated, [5] pooled draws, [6] T, [7] slabs whose weight is 0 */
+  int64_t info[8];
+} s4b_check_out;
+int S4B_FN(predict_check)(s4b_sampler* s, const s4b_check_in* in, s4b_check_out* out);
+
 /* extension (R: loo::loo() on the rows-times-draws log-likelihood matrix, formed on the device): PSIS-LOO, Pareto-smoothed importance-sampling
  * leave-one-out, per row over the draws of `s` and its peers, pooled as predict_quantiles pools them (the draws of `s`, then the peers' in their order,
  * S in all, S <= 16384).  It follows loo's do_psis_i / psis_smooth_tail / gpdfit (Vehtari, Simpson, Gelman, Yao, Gabry; the fit: Zhang & Stephens

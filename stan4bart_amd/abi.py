@@ -159,6 +159,19 @@ class PpdIn(C.Structure):              # s4b_ppd_in
                 ("scratch_bytes", C.c_int64)]
 
 
+class CheckIn(C.Structure):            # s4b_check_in
+    _fields_ = [("rows", SummaryIn), ("y", c_double_p), ("sigma", c_double_p), ("row_scale", c_double_p), ("noise_key", C.c_uint64),
+                ("row_weights", c_double_p), ("n_thresholds", C.c_int32), ("thresholds", c_double_p), ("bin_index", C.c_int32),
+                ("n_probs", C.c_int32), ("probs", c_double_p), ("n_peers", C.c_int32), ("peers", C.POINTER(C.c_void_p)),
+                ("peer_dense_coef", C.POINTER(c_double_p)), ("peer_ell_coef", C.POINTER(c_double_p)), ("peer_sigma", C.POINTER(c_double_p)),
+                ("scratch_bytes", C.c_int64)]
+
+
+class CheckOut(C.Structure):           # s4b_check_out
+    _fields_ = [("mean", c_double_p), ("m2", c_double_p), ("quantiles", c_double_p), ("draws", c_double_p), ("observed", c_double_p),
+                ("weight", C.c_double), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
 class PpdOut(C.Structure):             # s4b_ppd_out
     _fields_ = [("quantiles", c_double_p), ("lpd", c_double_p), ("lmean", c_double_p), ("lm2", c_double_p), ("pit", c_double_p),
                 ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
@@ -201,6 +214,7 @@ SPREAD_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", 
 SPREAD_THRESHOLDS_MAX = 64             # S4B_SPREAD_THRESHOLDS_MAX: thresholds of one s4b_predict_spread call at most
 SPREAD_SLAB = 128                      # S4B_SPREAD_SLAB: rows per slab of the moments' and the bins' fold
 SPREAD_BIN_INDEX = {"auto": 0, "compare": 1, "search": 2}
+CHECK_INFO = SPREAD_INFO               # (s4b_check_out.info has s4b_spread_out.info's layout)
 PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
 LOO_INFO = QUANTILE_INFO               # (s4b_loo_out.info likewise; rows_per_sort: rows per workgroup of k_loo_rows)
 LOO_OUTPUTS = ("elpd_loo", "pareto_k", "lpd", "ess")
@@ -454,6 +468,7 @@ class Sampler:
             "predict_groups": [vp, C.POINTER(GroupsIn), C.POINTER(GroupsOut)],
             "predict_projection": [vp, C.POINTER(ProjectionIn), C.POINTER(ProjectionOut)],
             "predict_spread": [vp, C.POINTER(SpreadIn), C.POINTER(SpreadOut)],
+            "predict_check": [vp, C.POINTER(CheckIn), C.POINTER(CheckOut)],
             "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
             "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
             "predict_convergence": [vp, C.POINTER(ConvIn), C.POINTER(ConvOut)],
@@ -1215,6 +1230,85 @@ class Sampler:
         return dict(res, names=self.spread_names(T), weight=float(out.weight), thresholds=th, draws_pooled=int(out.num_samples),
                     info=dict(self.spread_info))
 
+    def check_draws(self) -> int:
+        """The kept draws of this sampler, as ``s4b_predict_check``'s query form reports them."""
+        probe = CheckOut()
+        self._check(self._f("predict_check")(self._h, None, C.byref(probe)))
+        return int(probe.num_samples)
+
+    @staticmethod
+    def check_names(n_thresholds: int):
+        """The statistics of ``s4b_predict_check``'s matrix in row order: 7 + T names (``observed`` holds the first 5 + T)."""
+        return ["mean", "sd", "m3", "min", "max"] + [f"share_above[{j}]" for j in range(int(n_thresholds))] + ["disc_rep", "disc_obs"]
+
+    def predict_check(self, x_test: np.ndarray, y=None, thresholds=(), probs=(), sigma=None, row_scale=None, noise_key: int = 0, weights=None,
+                      peers=(), peer_sigma=None, peer_dense_coef=None, peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None,
+                      ell_value=None, ell_coef=None, link: int = 0, outputs=("mean", "m2", "observed"), route="auto", stage_nodes: int = 0,
+                      scratch_bytes: int = 0, bin_index="auto") -> dict:
+        """``s4b_predict_check``: posterior predictive checks over the kept draws of this sampler and of ``peers``, pooled in ONE device call as
+        ``predict_ppd`` pools them.  Per pooled draw the statistics of the replicate y_rep ACROSS THE ROWS — link 0: z + sigma row_scale e, the bits
+        ``predict_ppd`` sorts under the same ``noise_key``; link 1: 1 where a uniform of the same block is <= Phi(z) —: the weighted mean, sd, third
+        central moment, min, max, the share of the weight strictly above each of the T <= 64 ascending ``thresholds`` (T = 0 under link 1), and
+        the realised discrepancy of the replicate and of ``y`` [rows] (link 0: chi^2, link 1: deviance); over the draws the mean, m2 and ``probs``
+        quantiles of each of these 7 + T series.  ``weights`` None (1) or [rows], non-negative, not all 0.  ``outputs``: any of "mean", "m2",
+        "observed" (the first 5 + T statistics of ``y`` itself); the matrix ``draws`` [(7 + T) x pooled draws] is always returned.  Returns names,
+        draws, observed, mean, m2, quantiles [Q x (7 + T)] or None, weight, thresholds, ``draws_pooled`` and info: CHECK_INFO."""
+        fn = getattr(self._lib, self._pfx + "predict_check", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_check")
+
+        def draws(smp):
+            probe = CheckOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        unknown = set(outputs) - {"mean", "m2", "observed"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if pr.ndim != 1:
+            raise ValueError(f"probs must be a vector, not shape {pr.shape}")
+        th = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+        if th.ndim != 1:
+            raise ValueError(f"thresholds must be a vector, not shape {th.shape}")
+        if isinstance(bin_index, str) and bin_index not in SPREAD_BIN_INDEX:
+            raise ValueError(f"bin_index must be one of {', '.join(SPREAD_BIN_INDEX)}, not {bin_index!r}")
+        peers = list(peers)
+        own = draws(self)
+        rows_in, keep, rows, _ = self._summary_in(own, x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, None, route,
+                                                   stage_nodes, 0)
+
+        def vector(a, n, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+            if a.shape != (n,):
+                raise ValueError(f"{what} must have shape ({n},), not {a.shape}")
+            return a
+
+        pdc, hold_d = _peer_tables(peers, draws, peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
+        pec, hold_e = _peer_tables(peers, draws, peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
+        psg, hold_s = _peer_tables(peers, draws, None if peer_sigma is None else [np.asarray(t, dtype=np.float64).reshape(-1, 1) for t in peer_sigma], 1, "peer_sigma")
+        handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
+        yy, sg, rs, ww = vector(y, rows, "y"), vector(sigma, own, "sigma"), vector(row_scale, rows, "row_scale"), vector(weights, rows, "weights")
+        S = own + sum(draws(p) for p in peers)
+        T = len(th)
+        Tc = min(T, SPREAD_THRESHOLDS_MAX)          # (more thresholds are refused by the library: no array is sized by them)
+        M = 7 + Tc
+        res = dict(draws=np.zeros((M, S)), observed=np.zeros(5 + Tc) if "observed" in outputs else None, mean=np.zeros(M) if "mean" in outputs else None,
+                   m2=np.zeros(M) if "m2" in outputs else None, quantiles=np.zeros((len(pr), M)) if len(pr) else None)
+        arg = CheckIn(rows=rows_in, y=_dp(yy), sigma=_dp(sg), row_scale=_dp(rs), noise_key=int(noise_key) & 0xFFFFFFFFFFFFFFFF, row_weights=_dp(ww),
+                      n_thresholds=T, thresholds=_dp(th) if T else None, bin_index=int(SPREAD_BIN_INDEX.get(bin_index, bin_index)), n_probs=len(pr),
+                      probs=_dp(pr), n_peers=len(peers), peers=handles if peers else None, peer_dense_coef=pdc, peer_ell_coef=pec, peer_sigma=psg,
+                      scratch_bytes=int(scratch_bytes))
+        out = CheckOut(mean=_dp(res["mean"]), m2=_dp(res["m2"]), quantiles=_dp(res["quantiles"]), draws=_dp(res["draws"]), observed=_dp(res["observed"]))
+        self.check_info = dict(zip(CHECK_INFO, [0] * 8))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        self.check_info = dict(zip(CHECK_INFO, (int(v) for v in out.info)))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep, hold_d, hold_e, hold_s, yy, sg, rs, ww
+        return dict(res, names=self.check_names(T), weight=float(out.weight), thresholds=th, draws_pooled=int(out.num_samples),
+                    info=dict(self.check_info))
+
     def predict_ppd(self, x_test: np.ndarray, probs=(), y=None, sigma=None, row_scale=None, noise_key: int = 0, peers=(), peer_sigma=None,
                     peer_dense_coef=None, peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None, ell_coef=None,
                     link: int = 0, lpd: bool = True, moments: bool = True, pit: Optional[bool] = None, route="auto", stage_nodes: int = 0,
@@ -1512,6 +1606,9 @@ class StoredSampler:
     spread_draws = Sampler.spread_draws
     spread_names = staticmethod(Sampler.spread_names)
     predict_spread = Sampler.predict_spread
+    check_draws = Sampler.check_draws
+    check_names = staticmethod(Sampler.check_names)
+    predict_check = Sampler.predict_check
     predict_ppd = Sampler.predict_ppd
     predict_loo = Sampler.predict_loo
     predict_convergence = Sampler.predict_convergence

@@ -1635,6 +1635,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 #include "dev_groups.inc"
 #include "readout_projection.inc"
 #include "readout_spread.inc"
+#include "readout_check.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
 static void use_device(int device) {
@@ -2750,6 +2751,8 @@ class DevHip {
   void predict_projection(const ProjectionCall& c) { projection_run(stream_, a_.P, c, launches_); }
   // s4b_predict_spread (readout_spread.inc), likewise
   void predict_spread(const SpreadCall& c) { spread_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_check (readout_check.inc), likewise
+  void predict_check(const CheckCall& c) { check_run(stream_, a_.P, c, launches_); }
   // s4b_predict_ppd (dev_ppd.inc), likewise
   void predict_ppd(const PpdCall& c) { ppd_run(stream_, a_.P, c, launches_); }
   // s4b_predict_loo (dev_loo.inc), likewise

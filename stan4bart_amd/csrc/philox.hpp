@@ -94,6 +94,13 @@ S4B_PHX double philox_normal(uint32_t k0, uint32_t k1, uint64_t row, uint32_t dr
   const double u1 = philox_u53(r.v[0], r.v[1]), u2 = philox_u53(r.v[2], r.v[3]);
   return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
 }
+// The (0, 1] uniform of element (row, draw) of a posterior predictive check with a binary response (s4b_predict_check): philox_u53 of
+// the FIRST TWO words of philox_normal's block, the same counter and key (u1 there).  A pure function of (key, row, draw).
+S4B_PHX double philox_uniform(uint32_t k0, uint32_t k1, uint64_t row, uint32_t draw) {
+  const Philox4 c = {{(uint32_t)row, (uint32_t)(row >> 32), draw, PPD_TAG}};
+  const Philox4 r = philox4x32_10(c, k0, k1);
+  return philox_u53(r.v[0], r.v[1]);
+}
 
 }  // namespace s4b
 

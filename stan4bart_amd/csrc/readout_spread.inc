@@ -54,6 +54,28 @@ struct SpreadDev {
   int T; double W;
 };
 
+// bin(x) = #{j : x > t_j} of the N values a lane holds, added onto bin[] (the caller's 0): SEARCH false counts the compares against thr[0 .. T), a
+// scalar load per threshold shared by the N values; SEARCH true walks the thresholds staged in LDS at `tl` in ceil(log2(T + 1)) steps from `top`, the
+// largest power of two <= T.  Both give the same bin.  (k_spread_reduce's, and readout_check.inc's k_check_reduce's.)
+template <bool SEARCH, int N>
+__device__ __forceinline__ void sp_bins(const double (&xs)[N], int (&bin)[N], int T, int top, const double* thr, const double* tl) {
+  if (SEARCH) {
+    for (int step = top; step; step >>= 1) {
+#pragma unroll
+      for (int u = 0; u < N; ++u) {
+        const int q = bin[u] + step;
+        if (q <= T && xs[u] > tl[q - 1]) bin[u] = q;
+      }
+    }
+  } else {
+    for (int j = 0; j < T; ++j) {
+      const double t = thr[j];
+#pragma unroll
+      for (int u = 0; u < N; ++u) bin[u] += xs[u] > t ? 1 : 0;
+    }
+  }
+}
+
 template <bool BINS, bool SEARCH>
 __global__ __launch_bounds__(SP_BLOCK) void k_spread_reduce(SpreadDev a) {
   extern __shared__ __attribute__((aligned(16))) double sp_lds[];                  // cw [T + 1][64], cs [T + 1][64], then (SEARCH) the thresholds [T]
@@ -90,23 +112,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spread_reduce(SpreadDev a) {
       ws[u] = w ? w[q] : 1.0;
       bin[u] = 0;
     }
-    if (BINS) {
-      if (SEARCH) {
-        for (int step = top; step; step >>= 1) {
-#pragma unroll
-          for (int u = 0; u < SP_AHEAD; ++u) {
-            const int q = bin[u] + step;
-            if (q <= T && xs[u] > tl[q - 1]) bin[u] = q;
-          }
-        }
-      } else {
-        for (int j = 0; j < T; ++j) {
-          const double t = thr[j];
-#pragma unroll
-          for (int u = 0; u < SP_AHEAD; ++u) bin[u] += xs[u] > t ? 1 : 0;
-        }
-      }
-    }
+    if (BINS) sp_bins<SEARCH, SP_AHEAD>(xs, bin, T, top, thr, tl);
 #pragma unroll
     for (int u = 0; u < SP_AHEAD; ++u) {
       if (r + u < rows) {                                                          // (the same for every lane)

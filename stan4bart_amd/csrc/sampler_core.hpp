@@ -156,6 +156,22 @@ struct SpreadCall {
   double* mean; double* m2; double* quantiles; double* draws;          // [4 + 2 T], [4 + 2 T], [Q x (4 + 2 T)], [(4 + 2 T) x S]
 };
 
+// does the device layer form the posterior predictive check per pooled draw (s4b_predict_check)?  As has_predict_spread.
+template <class D, class = void> struct has_predict_check : std::false_type {};
+template <class D> struct has_predict_check<D, std::void_t<decltype(&D::predict_check)>> : std::true_type {};
+// one s4b_predict_check call as the device layer sees it: the rows, y, sigma per POOLED draw (link 0) and the row scale as PpdCall's, the validated
+// thresholds [T] ascending, the row weights (NULL: 1), W > 0 and the slabs without weight as the host formed them; draws is always given, every
+// other output NULL where it was not asked for
+struct CheckCall {
+  SummaryCall rows;
+  const double* y; const double* sigma; const double* rowScale;          // [nT]; [S] or NULL (link 1); [nT] or NULL
+  uint64_t noiseKey;
+  const double* thresholds; int T, binIndex;
+  const double* rowWeights; double W; int64_t zeroSlabs;
+  int Q; const double* probs; int64_t scratchBytes;
+  double* mean; double* m2; double* quantiles; double* draws; double* observed;          // [7 + T], [7 + T], [Q x (7 + T)], [(7 + T) x S], [5 + T]
+};
+
 // does the device layer form the posterior predictive read-out over the pooled kept draws (s4b_predict_ppd)?  As has_predict_quantiles.
 template <class D, class = void> struct has_predict_ppd : std::false_type {};
 template <class D> struct has_predict_ppd<D, std::void_t<decltype(&D::predict_ppd)>> : std::true_type {};
@@ -979,6 +995,72 @@ class SamplerCore {
       out->num_samples = S;
       return S;
     } else throw std::invalid_argument("predict_spread: this device layer has no spread kernels (the across-row read-out is formed by the HIP library only)");
+  }
+  // s4b_predict_check: posterior predictive checks — per pooled draw the weighted mean, standard deviation, third central moment and extremes of the
+  // replicate y_rep ACROSS THE ROWS, the share of the weight above each of up to 64 thresholds and a realised discrepancy beside the observed one; the
+  // same statistics of y itself; of the per-draw series the mean, m2 and type-7 quantiles over the draws.  Pooled like predict_ppd.  W and the slabs
+  // without weight are formed here, in row order.  Everything is validated here, before any launch.
+  int64_t predict_check(const s4b_check_in* in, s4b_check_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_check: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    out->weight = 0.0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in || !out->draws) return own;          // query
+    {          // (the checks run on every device layer; the layer without check kernels refuses what passed them)
+      const std::string who = "predict_check";
+      const s4b_summary_in* rw = &in->rows;
+      if (rw->n_weights != 0) throw std::invalid_argument(who + ": rows.n_weights must be 0 (the row weights are row_weights), not " + std::to_string(rw->n_weights));
+      check_summary_rows(rw, who, 0);
+      const int T = in->n_thresholds;
+      if (T < 0 || T > S4B_SPREAD_THRESHOLDS_MAX)
+        throw std::invalid_argument(who + ": n_thresholds must lie in [0, " + std::to_string(S4B_SPREAD_THRESHOLDS_MAX) + "], not " + std::to_string(T));
+      if (T > 0 && rw->link != 0) throw std::invalid_argument(who + ": n_thresholds must be 0 under link 1 (a binary replicate is 0 or 1: its mean is the share of ones), not " + std::to_string(T));
+      if (T > 0 && !in->thresholds) throw std::invalid_argument(who + ": NULL thresholds");
+      for (int j = 0; j < T; ++j) {
+        if (std::isnan(in->thresholds[j])) throw std::invalid_argument(who + ": threshold " + std::to_string(j) + " is a NaN");
+        if (j > 0 && !(in->thresholds[j] > in->thresholds[j - 1])) throw std::invalid_argument(who + ": the thresholds are not strictly ascending at index " + std::to_string(j));
+      }
+      if (in->bin_index < 0 || in->bin_index > 2) throw std::invalid_argument(who + ": bin_index must be 0 (the library's choice), 1 (compares) or 2 (search), not " + std::to_string(in->bin_index));
+      if (in->n_probs < 0 || in->n_probs > 16) throw std::invalid_argument(who + ": between 0 and 16 probs per call, not " + std::to_string(in->n_probs));
+      if (in->n_probs > 0 && !in->probs) throw std::invalid_argument(who + ": NULL probs");
+      for (int j = 0; j < in->n_probs; ++j)
+        if (!(in->probs[j] >= 0.0 && in->probs[j] <= 1.0)) throw std::invalid_argument(who + ": prob " + std::to_string(in->probs[j]) + " outside [0, 1]");
+      if (in->n_probs > 0 && !out->quantiles) throw std::invalid_argument(who + ": n_probs > 0 needs quantiles");
+      if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
+      if (!in->y) throw std::invalid_argument(who + ": NULL y (a check holds the replicate against the observed responses)");
+      const int64_t nT = rw->n_test;
+      double W = 0.0, Ws = 0.0;          // in row order, in double: part of the definition
+      int64_t zeroSlabs = 0;
+      for (int64_t i = 0; i < nT; ++i) {
+        const double w = in->row_weights ? in->row_weights[i] : 1.0;
+        if (!(w >= 0.0) || std::isinf(w)) throw std::invalid_argument(who + ": weight " + std::to_string(w) + " of row " + std::to_string(i) + " is negative or not finite");
+        W += w; Ws += w;
+        if ((i + 1) % S4B_SPREAD_SLAB == 0 || i + 1 == nT) { zeroSlabs += Ws == 0.0; Ws = 0.0; }
+      }
+      if (!(W > 0.0)) throw std::invalid_argument(who + ": the weights sum to 0 (no row carries weight)");
+      const int np = in->n_peers;
+      const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
+      std::vector<double> sigma;
+      check_responses(who, rw, in->y, in->sigma, in->peer_sigma, in->row_scale, np, peers, S, sigma);
+      if constexpr (has_predict_check<Dev>::value) {
+        std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
+        bin_matrix(rw->x_test, (size_t)nT, xb);
+        CheckCall c{};
+        c.rows = summary_call(rw, xb, own); c.rows.info = out->info; c.rows.G = 0; c.rows.weights = nullptr;
+        c.y = in->y; c.sigma = rw->link == 0 ? sigma.data() : nullptr; c.rowScale = rw->link == 0 ? in->row_scale : nullptr; c.noiseKey = in->noise_key;
+        c.thresholds = in->thresholds; c.T = T; c.binIndex = in->bin_index;
+        c.rowWeights = in->row_weights; c.W = W; c.zeroSlabs = zeroSlabs;
+        c.Q = in->n_probs; c.probs = in->probs; c.scratchBytes = in->scratch_bytes;
+        c.mean = out->mean; c.m2 = out->m2; c.quantiles = in->n_probs > 0 ? out->quantiles : nullptr; c.draws = out->draws; c.observed = out->observed;
+        DrawPool pool;
+        pool_concat(c.rows, pool, rw, xb, np, peers, in->peer_dense_coef, in->peer_ell_coef, S);
+        out->weight = W;
+        dev_.predict_check(c);
+        out->num_samples = S;
+        return S;
+      } else throw std::invalid_argument("predict_check: this device layer has no check kernels (the replicate is formed by the HIP library only)");
+    }
   }
   // s4b_predict_ppd: the posterior predictive distribution of new observations at the rows — type-7 quantiles of y_rep = z + sigma row_scale e — and the
   // scores of held-out responses y (log predictive density, mean and squared deviations of the pointwise log-likelihood, PIT), per row over the

@@ -958,6 +958,99 @@ class Stan4bartFit:
                 out["coverage"] = float(np.mean((y >= lo) & (y <= hi)))
         return out
 
+    # ------------------------------------------------------------------ pp_check
+    def pp_check(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, y=None, thresholds=(), row_weights=None, obs_weights=None,
+                 probs=(0.025, 0.5, 0.975), seed: Optional[int] = None, return_draws: bool = False, offset=None, sample_new_levels: bool = True):
+        """Posterior predictive checks (rstanarm's ``pp_check``): do data replicated from the fitted model look like the observed ``y`` [rows]?  Per
+        posterior draw the replicate ``y_rep`` is formed on the device — continuous response: ``ev + sigma sqrt(1 / obs_weights) e``, the very
+        replicate ``predict_ppd`` summarises under the same ``seed``; binary response: Bernoulli(ev) — and reduced ACROSS THE ROWS without ever
+        being stored, in ONE pooled call (``s4b_predict_check``: the first chain's sampler with the others as its peers).  The statistics are the
+        weighted (``row_weights``: None or [rows], non-negative, not all 0) ``mean``, ``sd``, ``skewness``, ``min``, ``max``, ``share_above`` [T]
+        (the share of the weight strictly above each of the up to 64 ascending ``thresholds``; none for a binary response) and ``discrepancy``
+        (continuous: the chi^2 of Gelman, Meng and Stern; binary: the deviance).  Each view is a dict of ``observed`` (the statistic of ``y``), ``mean``,
+        ``sd`` (ddof 1) and ``quantiles`` [Q] over the draws and ``p_value``, the share of draws whose replicated statistic is >= the observed one
+        (``discrepancy``: the share with disc_rep >= disc_obs; its ``observed`` is the mean of disc_obs over the draws); with ``return_draws`` also
+        ``draws`` (``discrepancy``: ``draws`` and ``draws_obs``), chain after chain, and ``matrix`` [7 + T, draws] is returned.  Also ``names``,
+        ``probs``, ``thresholds``, ``weight``, ``draws`` (the pooled count), ``info``, ``noise_key`` and the ``seed`` that reproduces the whole
+        call.  Needs bart_args keepTrees."""
+        if not self.samplers:
+            raise ValueError("pp_check requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("pp_check needs x_bart, the rows of the BART predictors")
+        if y is None:
+            raise ValueError("pp_check needs y, the observed responses at the rows")
+        binary = self.family == "binomial"
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or len(pr) > 16 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of at most 16 values in [0, 1], not {probs!r}")
+        th = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        if th.ndim != 1 or len(th) > SPREAD_THRESHOLDS_MAX:
+            raise ValueError(f"'thresholds' must be a vector of at most {SPREAD_THRESHOLDS_MAX} values, not {len(th) if th.ndim == 1 else th.shape}")
+        if np.any(np.isnan(th)) or not np.all(th[1:] > th[:-1]):
+            raise ValueError("'thresholds' must be strictly ascending and hold no NaN")
+        if binary and len(th):
+            raise ValueError("pp_check takes no thresholds for a binary response: a replicate is 0 or 1, its mean is the share of ones")
+        x_bart = np.asarray(x_bart, dtype=np.float64)
+        rows = x_bart.shape[0]
+        y = np.asarray(y, dtype=np.float64)
+        if y.shape != (rows,) or not np.all(np.isfinite(y)):
+            raise ValueError(f"y must be {rows} finite values")
+        if binary and not np.all((y == 0.0) | (y == 1.0)):
+            raise ValueError("y must be 0 or 1 for a binary response")
+        w = None
+        if row_weights is not None:
+            w = np.asarray(row_weights, dtype=np.float64)
+            if w.shape != (rows,) or not np.all(np.isfinite(w)) or np.any(w < 0.0):
+                raise ValueError(f"row_weights must be [{rows}] finite non-negative values")
+            if not w.sum() > 0.0:
+                raise ValueError("row_weights sum to 0: no row carries weight")
+        row_scale = None
+        if obs_weights is not None:
+            ow = np.asarray(obs_weights, dtype=np.float64)
+            if ow.shape != (rows,) or not np.all(np.isfinite(ow) & (ow > 0.0)):
+                raise ValueError(f"obs_weights must be {rows} finite values > 0")
+            row_scale = 1.0 / np.sqrt(ow)                            # reference R/generics.R:452-459: sd = sigma sqrt(1 / w)
+        ss = np.random.SeedSequence(seed)                            # (predict_ppd's handling: the same seed gives the same noise_key)
+        noise_key = int(ss.generate_state(1, np.uint64)[0])
+        linear = self._summary_linear("ev", X, groups, offset, sample_new_levels, np.random.default_rng(ss))
+        first, others = linear(0), [linear(c) for c in range(1, len(self.samplers))]
+        sig = self.stan[self.par_names.index("aux.1")]               # [iter, chain]
+        r = self.samplers[0].predict_check(x_bart, y=y, thresholds=th, probs=pr, sigma=None if binary else sig[:, 0], row_scale=row_scale,
+                                           noise_key=noise_key, weights=w, peers=self.samplers[1:],
+                                           peer_sigma=None if binary else [sig[:, c] for c in range(1, len(self.samplers))],
+                                           peer_dense_coef=None if first["dense"] is None else [a["dense_coef"] for a in others],
+                                           peer_ell_coef=None if first["ell_index"] is None else [a["ell_coef"] for a in others], **first)
+        S, T, D, obs = r["draws_pooled"], len(th), r["draws"], r["observed"]
+        M = 7 + T
+        sd = np.sqrt(r["m2"] / (S - 1)) if S > 1 else np.full(M, np.nan)
+        q = r["quantiles"] if r["quantiles"] is not None else np.zeros((0, M))
+
+        def summary(v):
+            return {"mean": float(v.mean()), "sd": float(v.std(ddof=1)) if S > 1 else float("nan"),
+                    "quantiles": np.quantile(v, pr) if len(pr) else np.zeros(0)}
+
+        def view(m):
+            """A statistic of the matrix: the device's summary over the draws, the host's statistic of y, the p-value from the draws."""
+            out = {"observed": float(obs[m]), "mean": float(r["mean"][m]), "sd": float(sd[m]), "quantiles": q[:, m], "p_value": float(np.mean(D[m] >= obs[m]))}
+            if return_draws:
+                out["draws"] = D[m]
+            return out
+        with np.errstate(divide="ignore", invalid="ignore"):
+            skew = np.where(D[1] > 0.0, D[2] / (D[1] * D[1] * D[1]), np.nan)
+            skew_obs = float(obs[2] / obs[1] ** 3) if obs[1] > 0.0 else float("nan")
+            skewness = dict(summary(skew) if not np.any(np.isnan(skew)) else {"mean": float("nan"), "sd": float("nan"), "quantiles": np.full(len(pr), np.nan)},
+                            observed=skew_obs, p_value=float(np.mean(skew >= skew_obs)))
+        disc = dict(summary(D[5 + T]), observed=float(D[6 + T].mean()), p_value=float(np.mean(D[5 + T] >= D[6 + T])))
+        if return_draws:
+            skewness["draws"] = skew
+            disc.update(draws=D[5 + T], draws_obs=D[6 + T])
+        res = {"names": r["names"], "probs": pr, "thresholds": th, "weight": r["weight"], "draws": S, "info": r["info"], "noise_key": noise_key,
+               "seed": ss.entropy, "mean": view(0), "sd": view(1), "skewness": skewness, "min": view(3), "max": view(4),
+               "share_above": [view(5 + j) for j in range(T)], "discrepancy": disc}
+        if return_draws:
+            res["matrix"] = D
+        return res
+
     # ------------------------------------------------------------------ predict_loo
     def predict_loo(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, y=None, obs_weights=None, r_eff: float = 1.0,
                     sample_new_levels: bool = True, seed: Optional[int] = None):
