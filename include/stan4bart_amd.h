@@ -688,6 +688,68 @@ typedef struct {
 } s4b_check_out;
 int S4B_FN(predict_check)(s4b_sampler* s, const s4b_check_in* in, s4b_check_out* out);
 
+/* extension (R: the individual conditional expectation curves of pdbart's rows — ICE — and their summaries, formed on the device): PER-ROW RESPONSE
+ * CURVES along one or two BART predictors.  For row i, grid point g (which assigns grid[g + w * n_grid] to predictor vars[w], as partial_dependence's
+ * grid does) and pooled draw k
+ *     v(i, g, k) = partial_dependence's v: z (link 0) or Phi(z) (link 1), z = bart(row i with x[vars[w]] replaced by the grid point's values; draw k)
+ *                  + the linear parts of predict_summary at row i, draw k — THE VARIED PREDICTORS ARE BART PREDICTORS ONLY, the linear parts stay at
+ *                  the row's own values,
+ *     c(i, g, k) = v(i, g, k) - v(i, a, k)     with anchor = a in [0, n_grid): the curve centred at grid point a; anchor = -1: c = v.
+ * The draws are those of `s` and its peers, pooled as predict_quantiles pools them (rows, peers, their coefficient tables, probs and scratch_bytes are
+ * its input; rows.n_weights 0; n_probs may be 0).  in = NULL is the query form: num_samples of `s` alone.  Outputs, each NULL where it is not wanted
+ * (a call with every output NULL asks for nothing and is refused):
+ *   mean[i * n_grid + g], m2[...]             mean and sum of squared deviations of c(i, g, .) over the S pooled draws (two passes; variance m2 / (S - 1))
+ *   quantiles[(j * n_test + i) * n_grid + g]  R's type 7 of c(i, g, .), 0 <= n_probs <= 16; required where n_probs > 0
+ *   p_max[i * n_grid + g], p_min[...]         the share of the draws in which g is the LOWEST grid index that attains the row's maximum (minimum) of
+ *                                             c(i, ., k) over the grid: an integer count divided by S, exact; the shares of a row add up to 1
+ *   range_mean[i], range_m2[i], range_quantiles[j * n_test + i]     the same summaries of r(i, k) = max_g c(i, g, k) - min_g c(i, g, k)
+ * THE ORDER OF THE ADDITIONS per (row, grid point, draw) is fixed and depends on nothing else — not on n_grid, the other grid points, the chunking,
+ * the route or the kind of sampler.  With the trees of draw k ordered as partial_dependence orders them (those without a rule on a varied predictor in
+ * ascending index, then the others in ascending index):
+ *   anchor = -1, or link 1:  base = the leaf values of the first group added in that order from 0.0 with the row's own bins; f_g = base + the leaf values
+ *       of the second group in that order under grid point g; z_g = (f_g, or (f_g + 0.5) * range_k + min_k for a continuous response) + lin, lin =
+ *       offset[i] (or 0.0) + the dense and ELL terms in predict_summary's order; v_g = z_g or Phi(z_g) = erfc(-z_g / sqrt 2) / 2; c = v_g - v_a.
+ *   anchor >= 0 under link 0:  s_g = the leaf values of the second group alone added in that order from 0.0; c = range_k * (s_g - s_a) (range_k = 1 for a
+ *       binary response): predict_contrast's formula.  The first group and the linear parts cancel and are not evaluated.
+ * Hence c(i, a, k) is exactly +0.0, two grid points with equal bins give bit-equal curves, and a call with one varied predictor, n_grid = 2 and anchor = 0
+ * returns at g = 1 the bits predict_contrast returns for arm 1 = grid point 1, arm 0 = grid point 0 (link 0, no arm-0 linear part).
+ * The rows are processed in chunks of C rows whose values (C x n_grid x S doubles) are the only rows-times-draws storage beside the ranges (C x S):
+ * C = scratch / (8 S n_grid) rounded down to a multiple of 64, at least 64, at most n_test, scratch = scratch_bytes or the library's own limit (512 MiB: DESIGN.md 5.16), whichever is smaller.  A call
+ * whose smallest scratch 8 x 64 x S x n_grid exceeds S4B_CURVES_SCRATCH_MAX is refused: the grid cannot be split, the extremes need all of it.
+ * Refused before anything is launched, on every device layer, info left all zero: n_vars outside {1, 2}, a predictor outside [0, p), two equal
+ * predictors, n_grid outside [1, 64], a NULL grid or a NaN in it (+-inf allowed), anchor outside [-1, n_grid), n_probs outside [0, 16] or a prob
+ * outside [0, 1], n_probs > 0 without quantiles, range_quantiles without probs, rows.n_weights != 0, negative scratch_bytes, and whatever
+ * predict_quantiles refuses of the rows and the peers (S <= 16384).  Two calls, both routes, live and stored samplers, any chunking return the same
+ * bits.  Device memory: DESIGN.md 5.16. */
+#define S4B_CURVES_SCRATCH_MAX ((int64_t)1 << 30)   /* 1 GiB: the smallest value scratch of one s4b_predict_curves call at most */
+typedef struct {
+  s4b_summary_in rows;            /* n_weights 0 */
+  int32_t n_vars, vars[2], n_grid;   /* as s4b_pd_in */
+  const double* grid;             /* n_grid x n_vars, column-major */
+  int32_t anchor;                 /* -1, or the grid index the curves are centred at */
+  int32_t n_probs;                /* 0 .. 16 */
+  const double* probs;
+  int32_t n_peers;
+  s4b_sampler* const* peers;
+  const double* const* peer_dense_coef;
+  const double* const* peer_ell_coef;
+  int64_t scratch_bytes;
+} s4b_curves_in;
+typedef struct {
+  double* mean; double* m2;       /* n_test x n_grid each, row-major; independently NULL */
+  double* quantiles;              /* n_probs x n_test x n_grid; NULL when n_probs = 0 */
+  double* p_max; double* p_min;   /* n_test x n_grid each; independently NULL */
+  double* range_mean; double* range_m2;   /* n_test each; independently NULL */
+  double* range_quantiles;        /* n_probs x n_test, prob-major; or NULL */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did: [0] route of the value kernel (1 LDS-staged, 2 global; 0: no tree was walked — link 0, an anchor and no affected tree),
+   * [1] rows per chunk C, [2] chunks, [3] (rows sorted side by side per workgroup) << 32 | draws padded to a power of two, [4] nodes of the largest
+   * pooled draw, [5] kernel launches, [6] bytes of device memory the call allocated, [7] the trees with a rule on a varied predictor: (the most in one
+   * draw) << 32 | (their sum over the pooled draws) */
+  int64_t info[8];
+} s4b_curves_out;
+int S4B_FN(predict_curves)(s4b_sampler* s, const s4b_curves_in* in, s4b_curves_out* out);
+
 /* extension (R: loo::loo() on the rows-times-draws log-likelihood matrix, formed on the device): PSIS-LOO, Pareto-smoothed importance-sampling
  * leave-one-out, per row over the draws of `s` and its peers, pooled as predict_quantiles pools them (the draws of `s`, then the peers' in their order,
  * S in all, S <= 16384).  It follows loo's do_psis_i / psis_smooth_tail / gpdfit (Vehtari, Simpson, Gelman, Yao, Gabry; the fit: Zhang & Stephens

@@ -172,6 +172,19 @@ class CheckOut(C.Structure):           # s4b_check_out
                 ("weight", C.c_double), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
 
 
+class CurvesIn(C.Structure):           # s4b_curves_in
+    _fields_ = [("rows", SummaryIn), ("n_vars", C.c_int32), ("vars", C.c_int32 * 2), ("n_grid", C.c_int32), ("grid", c_double_p),
+                ("anchor", C.c_int32), ("n_probs", C.c_int32), ("probs", c_double_p), ("n_peers", C.c_int32),
+                ("peers", C.POINTER(C.c_void_p)), ("peer_dense_coef", C.POINTER(c_double_p)), ("peer_ell_coef", C.POINTER(c_double_p)),
+                ("scratch_bytes", C.c_int64)]
+
+
+class CurvesOut(C.Structure):          # s4b_curves_out
+    _fields_ = [("mean", c_double_p), ("m2", c_double_p), ("quantiles", c_double_p), ("p_max", c_double_p), ("p_min", c_double_p),
+                ("range_mean", c_double_p), ("range_m2", c_double_p), ("range_quantiles", c_double_p), ("num_samples", C.c_int64),
+                ("info", C.c_int64 * 8)]
+
+
 class PpdOut(C.Structure):             # s4b_ppd_out
     _fields_ = [("quantiles", c_double_p), ("lpd", c_double_p), ("lmean", c_double_p), ("lm2", c_double_p), ("pit", c_double_p),
                 ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
@@ -215,6 +228,9 @@ SPREAD_THRESHOLDS_MAX = 64             # S4B_SPREAD_THRESHOLDS_MAX: thresholds o
 SPREAD_SLAB = 128                      # S4B_SPREAD_SLAB: rows per slab of the moments' and the bins' fold
 SPREAD_BIN_INDEX = {"auto": 0, "compare": 1, "search": 2}
 CHECK_INFO = SPREAD_INFO               # (s4b_check_out.info has s4b_spread_out.info's layout)
+CURVES_INFO = QUANTILE_INFO[:7] + ("device_bytes", "largest_affected", "total_affected")          # (the last two share info[7], as in PD_INFO)
+CURVES_OUTPUTS = ("mean", "m2", "quantiles", "p_max", "p_min", "range_mean", "range_m2", "range_quantiles")
+CURVES_SCRATCH_MAX = 1 << 30           # S4B_CURVES_SCRATCH_MAX: the curves of 64 rows (8 x 64 x pooled draws x grid points) at most
 PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
 LOO_INFO = QUANTILE_INFO               # (s4b_loo_out.info likewise; rows_per_sort: rows per workgroup of k_loo_rows)
 LOO_OUTPUTS = ("elpd_loo", "pareto_k", "lpd", "ess")
@@ -469,6 +485,7 @@ class Sampler:
             "predict_projection": [vp, C.POINTER(ProjectionIn), C.POINTER(ProjectionOut)],
             "predict_spread": [vp, C.POINTER(SpreadIn), C.POINTER(SpreadOut)],
             "predict_check": [vp, C.POINTER(CheckIn), C.POINTER(CheckOut)],
+            "predict_curves": [vp, C.POINTER(CurvesIn), C.POINTER(CurvesOut)],
             "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
             "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
             "predict_convergence": [vp, C.POINTER(ConvIn), C.POINTER(ConvOut)],
@@ -1309,6 +1326,70 @@ class Sampler:
         return dict(res, names=self.check_names(T), weight=float(out.weight), thresholds=th, draws_pooled=int(out.num_samples),
                     info=dict(self.check_info))
 
+    def curves_draws(self) -> int:
+        """The kept draws of this sampler, as ``s4b_predict_curves``' query form reports them."""
+        probe = CurvesOut()
+        self._check(self._f("predict_curves")(self._h, None, C.byref(probe)))
+        return int(probe.num_samples)
+
+    def predict_curves(self, x_test: np.ndarray, vars, grid, anchor=None, probs=(), outputs=CURVES_OUTPUTS, peers=(), peer_dense_coef=None,
+                       peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None, ell_coef=None, link: int = 0,
+                       route="auto", stage_nodes: int = 0, scratch_bytes: int = 0) -> dict:
+        """``s4b_predict_curves``: per row the response curve along the BART predictors ``vars`` (one index or two) — ``partial_dependence``'s value
+        per row and grid point instead of averaged over the rows — over the kept draws of this sampler and of ``peers``, pooled in ONE device call
+        as ``predict_quantiles`` pools them.  ``grid`` [G] or [G x len(vars)], G <= 64; ``anchor`` None or the grid index the curves are centred
+        at (c = v - v at the anchor); ``probs`` up to 16; ``outputs`` names what is asked for (CURVES_OUTPUTS; the quantile outputs need probs);
+        Returns dict(mean, m2, p_max, p_min [rows x G],
+        quantiles [Q x rows x G], range_mean, range_m2 [rows], range_quantiles [Q x rows] (None where not asked for), draws: the pooled count,
+        info: CURVES_INFO)."""
+        fn = getattr(self._lib, self._pfx + "predict_curves", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_curves")
+
+        def draws(smp):
+            probe = CurvesOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        unknown = set(outputs) - set(CURVES_OUTPUTS)
+        if unknown:
+            raise ValueError(f"outputs must be among {CURVES_OUTPUTS}, not {sorted(unknown)}")
+        pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if pr.ndim != 1:
+            raise ValueError(f"probs must be a vector, not shape {pr.shape}")
+        vs = np.atleast_1d(np.asarray(vars, dtype=np.int64))
+        if vs.ndim != 1 or len(vs) not in (1, 2):
+            raise ValueError(f"vars must be one predictor index or two, not {vars!r}")
+        gr = np.asarray(grid, dtype=np.float64)
+        if gr.ndim == 1:
+            gr = gr[:, None]
+        if gr.ndim != 2 or gr.shape[1] != len(vs):
+            raise ValueError(f"grid must be [G] or [G x {len(vs)}], not shape {np.shape(grid)}")
+        gr = np.asfortranarray(gr)
+        G = gr.shape[0]
+        peers = list(peers)
+        rows_in, keep, rows, _ = self._summary_in(draws(self), x_test, offset, dense, dense_coef, ell_index, ell_value, ell_coef, link, None, route,
+                                                   stage_nodes, 0)
+        pdc, hold_d = _peer_tables(peers, draws, peer_dense_coef, rows_in.n_dense, "peer_dense_coef")
+        pec, hold_e = _peer_tables(peers, draws, peer_ell_coef, rows_in.n_ell_coef if rows_in.n_ell else 0, "peer_ell_coef")
+        handles = (C.c_void_p * max(1, len(peers)))(*[p._h.value for p in peers])
+        Q = len(pr)
+        shapes = dict(mean=(rows, G), m2=(rows, G), quantiles=(Q, rows, G), p_max=(rows, G), p_min=(rows, G), range_mean=(rows,), range_m2=(rows,),
+                      range_quantiles=(Q, rows))
+        res = {k: (np.zeros(shapes[k]) if k in outputs else None) for k in CURVES_OUTPUTS}
+        spare = np.zeros(1)          # (what a count beyond the library's limits would fill: refused there, which needs a pointer)
+        ptr = {k: (None if v is None else _dp(v if v.size else spare)) for k, v in res.items()}
+        arg = CurvesIn(rows=rows_in, n_vars=len(vs), vars=(C.c_int32 * 2)(int(vs[0]), int(vs[-1]) if len(vs) > 1 else -1), n_grid=G, grid=_dp(gr),
+                       anchor=-1 if anchor is None else int(anchor), n_probs=Q, probs=_dp(pr),
+                       n_peers=len(peers), peers=handles if peers else None, peer_dense_coef=pdc, peer_ell_coef=pec, scratch_bytes=int(scratch_bytes))
+        out = CurvesOut(**ptr)
+        self.curves_info = dict(zip(CURVES_INFO, [0] * 10))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        w = [int(v) for v in out.info]
+        self.curves_info = dict(zip(CURVES_INFO, w[:3] + [w[3] >> 32, w[3] & 0xFFFFFFFF] + w[4:7] + [w[7] >> 32, w[7] & 0xFFFFFFFF]))          # (all zero after a refusal)
+        self._check(rc)
+        del keep, hold_d, hold_e, spare
+        return dict(res, draws=int(out.num_samples), info=dict(self.curves_info))
+
     def predict_ppd(self, x_test: np.ndarray, probs=(), y=None, sigma=None, row_scale=None, noise_key: int = 0, peers=(), peer_sigma=None,
                     peer_dense_coef=None, peer_ell_coef=None, offset=None, dense=None, dense_coef=None, ell_index=None, ell_value=None, ell_coef=None,
                     link: int = 0, lpd: bool = True, moments: bool = True, pit: Optional[bool] = None, route="auto", stage_nodes: int = 0,
@@ -1609,6 +1690,8 @@ class StoredSampler:
     check_draws = Sampler.check_draws
     check_names = staticmethod(Sampler.check_names)
     predict_check = Sampler.predict_check
+    curves_draws = Sampler.curves_draws
+    predict_curves = Sampler.predict_curves
     predict_ppd = Sampler.predict_ppd
     predict_loo = Sampler.predict_loo
     predict_convergence = Sampler.predict_convergence

@@ -172,6 +172,21 @@ struct CheckCall {
   double* mean; double* m2; double* quantiles; double* draws; double* observed;          // [7 + T], [7 + T], [Q x (7 + T)], [(7 + T) x S], [5 + T]
 };
 
+// does the device layer form the per-row response curves over the pooled kept draws (s4b_predict_curves)?  As has_predict_check.
+template <class D, class = void> struct has_predict_curves : std::false_type {};
+template <class D> struct has_predict_curves<D, std::void_t<decltype(&D::predict_curves)>> : std::true_type {};
+// one s4b_predict_curves call as the device layer sees it: the rows as QuantileCall.rows over the POOLED draws, the varied predictors, the grid binned
+// as rows are and the tree order of pd_tree_order per pooled draw as PdCall's, the anchor (-1: none), every output NULL where it was not asked for
+struct CurvesCall {
+  SummaryCall rows;
+  int V, vars[2], G, anchor; const uint16_t* gridBin;  // [V x G]
+  const int32_t* order; const int32_t* numBase;        // [S x T], [S]
+  int64_t maxAffected, totalAffected;
+  int Q; const double* probs; int64_t scratchBytes;
+  double* mean; double* m2; double* quantiles; double* pMax; double* pMin;          // [nT x G], [nT x G], [Q x nT x G], [nT x G], [nT x G]
+  double* rangeMean; double* rangeM2; double* rangeQuantiles;                       // [nT], [nT], [Q x nT]
+};
+
 // does the device layer form the posterior predictive read-out over the pooled kept draws (s4b_predict_ppd)?  As has_predict_quantiles.
 template <class D, class = void> struct has_predict_ppd : std::false_type {};
 template <class D> struct has_predict_ppd<D, std::void_t<decltype(&D::predict_ppd)>> : std::true_type {};
@@ -1060,6 +1075,75 @@ class SamplerCore {
         out->num_samples = S;
         return S;
       } else throw std::invalid_argument("predict_check: this device layer has no check kernels (the replicate is formed by the HIP library only)");
+    }
+  }
+  // s4b_predict_curves: per row the response curve along one or two BART predictors — partial_dependence's v(i,g,k) kept per row instead of averaged
+  // over the rows, optionally centred at an anchor grid point — summarised over the pooled draws per (row, grid point), and across the grid per draw
+  // (which point is highest / lowest, how far the curve ranges).  Pooled like predict_quantiles.  Everything is validated here, before any launch.
+  int64_t predict_curves(const s4b_curves_in* in, s4b_curves_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_curves: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in) return own;          // query
+    {          // (the checks run on every device layer; the layer without curve kernels refuses what passed them)
+      const std::string who = "predict_curves";
+      const s4b_summary_in* rw = &in->rows;
+      if (!out->mean && !out->m2 && !out->quantiles && !out->p_max && !out->p_min && !out->range_mean && !out->range_m2 && !out->range_quantiles)
+        throw std::invalid_argument(who + ": nothing asked for (every output is NULL)");
+      if (rw->n_weights != 0) throw std::invalid_argument(who + ": rows.n_weights must be 0 (the curves are per row), not " + std::to_string(rw->n_weights));
+      check_summary_rows(rw, who, 0);
+      if (in->n_vars != 1 && in->n_vars != 2) throw std::invalid_argument(who + ": one or two varied predictors, not " + std::to_string(in->n_vars));
+      for (int w = 0; w < in->n_vars; ++w)
+        if (in->vars[w] < 0 || in->vars[w] >= P_) throw std::invalid_argument(who + ": predictor " + std::to_string(in->vars[w]) + " outside [0, " + std::to_string(P_) + ")");
+      if (in->n_vars == 2 && in->vars[0] == in->vars[1]) throw std::invalid_argument(who + ": the two varied predictors must differ");
+      if (in->n_grid < 1 || in->n_grid > 64) throw std::invalid_argument(who + ": between 1 and 64 grid points per call, not " + std::to_string(in->n_grid));
+      if (!in->grid) throw std::invalid_argument(who + ": NULL grid");
+      const int V = in->n_vars, G = in->n_grid;
+      for (int x = 0; x < V * G; ++x) if (std::isnan(in->grid[x])) throw std::invalid_argument(who + ": the grid holds a NaN");
+      if (in->anchor < -1 || in->anchor >= G) throw std::invalid_argument(who + ": anchor " + std::to_string(in->anchor) + " outside [-1, " + std::to_string(G) + ")");
+      if (in->n_probs < 0 || in->n_probs > 16) throw std::invalid_argument(who + ": between 0 and 16 probs per call, not " + std::to_string(in->n_probs));
+      if (in->n_probs > 0 && !in->probs) throw std::invalid_argument(who + ": NULL probs");
+      for (int j = 0; j < in->n_probs; ++j)
+        if (!(in->probs[j] >= 0.0 && in->probs[j] <= 1.0)) throw std::invalid_argument(who + ": prob " + std::to_string(in->probs[j]) + " outside [0, 1]");
+      if (in->n_probs > 0 && !out->quantiles) throw std::invalid_argument(who + ": n_probs > 0 needs quantiles");
+      if (in->n_probs == 0 && (out->quantiles || out->range_quantiles)) throw std::invalid_argument(who + ": quantiles or range_quantiles given, but n_probs = 0");
+      if (in->scratch_bytes < 0) throw std::invalid_argument(who + ": negative scratch_bytes");
+      const int np = in->n_peers;
+      const int64_t S = pool_check(who, rw, np, in->peers != nullptr, peers, in->peer_dense_coef, in->peer_ell_coef);
+      if ((int64_t)8 * 64 * S * G > S4B_CURVES_SCRATCH_MAX)
+        throw std::invalid_argument(who + ": " + std::to_string(S) + " pooled draws x " + std::to_string(G) + " grid points need " + std::to_string((int64_t)8 * 64 * S * G) +
+                                    " bytes for the curves of 64 rows, at most " + std::to_string(S4B_CURVES_SCRATCH_MAX) + " (the grid cannot be split: fewer grid points or draws)");
+      if constexpr (has_predict_curves<Dev>::value) {
+        const int64_t nT = rw->n_test;
+        std::vector<uint16_t> xb((size_t)P_ * (size_t)nT);
+        bin_matrix(rw->x_test, (size_t)nT, xb);
+        std::vector<uint16_t> gridBin((size_t)(V * G));          // bin_matrix's rule: the number of cuts strictly below the value
+        for (int w = 0; w < V; ++w) {
+          const std::vector<double>& cu = cuts_[(size_t)in->vars[w]];
+          for (int g = 0; g < G; ++g) gridBin[(size_t)(w * G + g)] = (uint16_t)(std::lower_bound(cu.begin(), cu.end(), in->grid[w * G + g]) - cu.begin());
+        }
+        CurvesCall c{};
+        c.rows = summary_call(rw, xb, own); c.rows.info = out->info; c.rows.G = 0; c.rows.weights = nullptr;
+        c.V = V; c.vars[0] = in->vars[0]; c.vars[1] = V > 1 ? in->vars[1] : -1; c.G = G; c.anchor = in->anchor; c.gridBin = gridBin.data();
+        c.Q = in->n_probs; c.probs = in->probs; c.scratchBytes = in->scratch_bytes;
+        c.mean = out->mean; c.m2 = out->m2; c.quantiles = in->n_probs > 0 ? out->quantiles : nullptr; c.pMax = out->p_max; c.pMin = out->p_min;
+        c.rangeMean = out->range_mean; c.rangeM2 = out->range_m2; c.rangeQuantiles = out->range_quantiles;
+        DrawPool pool;
+        pool_concat(c.rows, pool, rw, xb, np, peers, in->peer_dense_coef, in->peer_ell_coef, S);
+        // the tree order of every pooled draw, each sampler's own trees
+        std::vector<int32_t> order, numBase, o, nb;
+        for (int x = -1; x < np; ++x) {
+          int64_t mx = 0, tot = 0;
+          (x < 0 ? this : peers[x])->pd_tree_order(V, in->vars, o, nb, mx, tot);
+          order.insert(order.end(), o.begin(), o.end()); numBase.insert(numBase.end(), nb.begin(), nb.end());
+          c.maxAffected = std::max(c.maxAffected, mx); c.totalAffected += tot;
+        }
+        c.order = order.data(); c.numBase = numBase.data();
+        dev_.predict_curves(c);
+        out->num_samples = S;
+        return S;
+      } else throw std::invalid_argument("predict_curves: this device layer has no curve kernels (the curves are formed by the HIP library only)");
     }
   }
   // s4b_predict_ppd: the posterior predictive distribution of new observations at the rows — type-7 quantiles of y_rep = z + sigma row_scale e — and the

@@ -16,7 +16,7 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from .abi import GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, PROJECTION_COLUMNS_MAX, SPREAD_THRESHOLDS_MAX, Sampler
+from .abi import CURVES_OUTPUTS, GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, PROJECTION_COLUMNS_MAX, SPREAD_THRESHOLDS_MAX, Sampler
 from .fit import GroupTerm, chain_seeds, hip_sampler_factory, make_sampler_args, make_z_csr, qr_back_transform
 from .rcompat import RRng
 
@@ -489,6 +489,63 @@ class Stan4bartFit:
         flat = combine_chains_f(pd)
         lower, upper = np.quantile(flat, probs, axis=1)
         return {"grid": grid, "pd": flat if combine_chains else pd, "mean": flat.mean(axis=1), "lower": lower, "upper": upper}
+
+    # ------------------------------------------------------------------ predict_curves
+    def predict_curves(self, var, x_bart=None, grid=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, anchor=None,
+                       probs=(0.025, 0.5, 0.975), type: str = "ev", sample_new_levels: bool = True, seed: Optional[int] = None):
+        """The individual conditional expectation curves of one BART predictor (``var`` an index into ``x_bart``'s columns) or of two jointly:
+        per row and grid value the prediction with the predictor(s) set to that value — ``partial_dependence`` before its average over the rows —
+        summarised on the device in ONE pooled call over all chains (``s4b_predict_curves``) without any [rows x draws] matrix.  ``grid`` as
+        ``partial_dependence`` takes it, at most 64 points (None: ``pd_default_grid`` of the column(s) of ``x_bart``).  ``anchor`` None or a grid
+        index: the curves are centred there, c = v - v(anchor) per draw — the effect of each grid value against the anchor's for this row, with
+        its own interval.  The fixed and random parts are ``predict_summary``'s and stay at the rows' own values.  Returns ``grid``; ``mean``,
+        ``sd`` (ddof 1), ``p_max``, ``p_min`` [rows, G] — the share of the draws in which a grid point is the row's highest / lowest (the lowest
+        index on an exact tie); ``quantiles`` [Q, rows, G]; ``range`` = dict(mean, sd, quantiles [Q, rows]) of max - min over the grid within
+        a draw; ``draws``, the pooled count, and ``info``."""
+        if type == "ppd":
+            raise ValueError("predict_curves does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("predict_curves requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_curves needs x_bart, the rows of the BART predictors")
+        x_bart = np.asarray(x_bart, dtype=np.float64)
+        rows, P = x_bart.shape
+        vs = [int(v) for v in np.atleast_1d(var)]
+        if len(vs) not in (1, 2) or len(set(vs)) != len(vs) or not all(0 <= v < P for v in vs):
+            raise ValueError(f"'var' must be one column index of x_bart or two different ones in [0, {P}), not {var!r}")
+        if grid is None:
+            grid = tuple(self.pd_default_grid(x_bart[:, v]) for v in vs)
+            grid = grid[0] if len(vs) == 1 else grid
+        if isinstance(grid, tuple):
+            if len(grid) != 2 or len(vs) != 2:
+                raise ValueError("a tuple of grid vectors is the product grid of a pair of predictors")
+            a, b = (np.asarray(t, dtype=np.float64).ravel() for t in grid)
+            grid = np.column_stack([np.repeat(a, len(b)), np.tile(b, len(a))])
+        grid = np.asarray(grid, dtype=np.float64)
+        pts = grid.reshape(-1, 1) if grid.ndim == 1 else grid
+        if pts.ndim != 2 or pts.shape[1] != len(vs) or not len(pts):
+            raise ValueError(f"grid must hold at least one point of {len(vs)} value(s), not shape {grid.shape}")
+        if len(pts) > PD_GRID_MAX:
+            raise ValueError(f"grid holds {len(pts)} points, at most {PD_GRID_MAX} per call (the extremes need the whole grid at once)")
+        if np.isnan(pts).any():
+            raise ValueError("grid holds a NaN")
+        if anchor is not None and not 0 <= int(anchor) < len(pts):
+            raise ValueError(f"'anchor' must be None or a grid index in [0, {len(pts)}), not {anchor!r}")
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of values in [0, 1], not {probs!r}")
+        outputs = tuple(k for k in CURVES_OUTPUTS if len(pr) or "quantiles" not in k)
+        linear = self._summary_linear(type, X, groups, offset, sample_new_levels, np.random.default_rng(seed))
+        first, others = linear(0), [linear(c) for c in range(1, len(self.samplers))]
+        r = self.samplers[0].predict_curves(x_bart, vs, pts, anchor=anchor, probs=pr, outputs=outputs, peers=self.samplers[1:],
+                                            peer_dense_coef=None if first["dense"] is None else [a["dense_coef"] for a in others],
+                                            peer_ell_coef=None if first["ell_index"] is None else [a["ell_coef"] for a in others], **first)
+        n = r["draws"]
+        sd = lambda m2: np.sqrt(m2 / (n - 1)) if n > 1 else np.full(m2.shape, np.nan)
+        return {"grid": grid, "mean": r["mean"], "sd": sd(r["m2"]), "p_max": r["p_max"], "p_min": r["p_min"], "quantiles": r["quantiles"], "probs": pr,
+                "range": {"mean": r["range_mean"], "sd": sd(r["range_m2"]), "quantiles": r["range_quantiles"]}, "draws": n, "info": r["info"]}
 
     # ------------------------------------------------------------------ predict_quantiles
     def predict_quantiles(self, x_bart=None, X=None, groups: Optional[Sequence[GroupTerm]] = None, offset=None, type: str = "ev",
