@@ -962,6 +962,27 @@ int S4B_FN(get_latent_mode)(s4b_sampler* s, int32_t* mode);
  * FALSE, report mean tree depth and leapfrogs per iteration) */
 int S4B_FN(get_nuts_stats)(s4b_sampler* s, double out[4]);
 
+/* extension: run-ahead helpers of the NUTS transition.  The leapfrog states of a transition are a function of its start point, momentum draw,
+ * step size and metric alone; a helper thread integrates one direction ahead while the sampler's thread builds the tree and consumes the
+ * finished states in the order the doublings ask for them; a state the helper has not finished when it is asked for is computed by the
+ * sampler's thread itself, as without a helper.  The chain is the same bit for bit with and without helpers.  n = 0: none; 1 (default): the
+ * backward direction; 2: both directions.  (TEST HOOK, not part of the contract and not reachable through the environment: n + 16 makes the
+ * sampler's thread wait for a helper's state instead of computing it, so that a test sees every state of a helper's direction come from the helper.)  The default is taken from the environment variable S4B_NUTS_HELPERS at create.
+ * Helpers exist only for a model whose gradient is closed-form host arithmetic (normal or flat coefficient prior, at most two coefficients per
+ * grouping term) in hmc_mode 0; every other sampler integrates inline whatever n says.  A process has at most 8 helper threads in all; a
+ * sampler that gets none integrates inline, and so does one whose thread may use no core but its own (a process bound to one core).  On Linux a
+ * helper is kept on the cores that share the last-level cache of the sampler's thread (its own affinity only, never the caller's).  A helper is created at the first transition that uses it, sleeps between transitions and is
+ * joined by free (or by a smaller n). */
+int S4B_FN(set_nuts_helpers)(s4b_sampler* s, int32_t n);
+/* {leapfrogs taken from a helper, leapfrogs of a helper's direction that the helper had not finished in time (computed by the sampler's
+ * thread itself; in the waiting mode: waited for, and counted as taken too), leapfrogs a helper computed that no tree consumed, transitions
+ * that ran without a helper} since creation */
+int S4B_FN(get_nuts_runahead)(s4b_sampler* s, int64_t out[4]);
+/* extension (process-wide): the host loops of a leapfrog (dense Gram product, leaf and merge loops) in their AVX2 form (on != 0) or their scalar
+ * form (0); both give the same bits.  Default: AVX2 where the CPU has it, unless the environment variable S4B_HOST_VECTOR is 0.  *effective
+ * (may be NULL) receives what is in force: 0 on a CPU without AVX2 whatever was asked.  on < 0 changes nothing and only reports. */
+int S4B_FN(set_host_vector)(int32_t on, int32_t* effective);
+
 /* measurement hook (no reference counterpart): runs `n_sweeps` extra BART sweeps with HIP events recorded on the
  * sampler's own stream around every kernel launch and returns, per kernel class
  * {stats, control, apply}: out[0..2] = average launch duration in microseconds, out[3..5] = launches timed,

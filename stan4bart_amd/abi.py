@@ -274,6 +274,17 @@ def _i32(a) -> np.ndarray:
 
 LATENT_MODES = {"exact": 0, "parallel": 1}      # bart_args latents -> s4b_set_latent_mode
 
+def set_host_vector(lib, prefix: str, on: Optional[bool]) -> bool:
+    """Process-wide: the host loops of a leapfrog in their AVX2 form (on) or their scalar form; both give the same bits.
+    Returns what is in force (False on a CPU without AVX2 whatever was asked).  on = None changes nothing and only reports."""
+    fn = getattr(lib, prefix + "set_host_vector")
+    fn.restype, fn.argtypes = C.c_int, [C.c_int32, c_int32_p]
+    eff = C.c_int32()
+    if fn(-1 if on is None else int(bool(on)), C.byref(eff)) != 0:
+        raise RuntimeError(getattr(lib, prefix + "last_error")().decode())
+    return bool(eff.value)
+
+
 @dataclass
 class SamplerArgs:
     """The six argument objects of ``stan4bart_create`` (reference R/stan4bart_fit.R:42) as numpy/python."""
@@ -474,6 +485,7 @@ class Sampler:
             "get_state": [vp, vp, i64, C.POINTER(i64)], "set_state": [vp, vp, i64],
             "set_trace": [vp, i32], "get_trace": [vp, i64, ip, C.POINTER(i64)],
             "get_leaf_assignment": [vp, i32, ip], "get_counters": [vp, C.POINTER(i64)], "get_nuts_stats": [vp, dp],
+            "set_nuts_helpers": [vp, i32], "get_nuts_runahead": [vp, C.POINTER(i64)],
             "profile_sweep": [vp, i32, dp], "profile_leapfrog": [vp, i32, dp],
             "set_progress": [vp, PROGRESS, vp], "set_device_sharing": [vp, i32],
             "set_tree_path": [vp, i32], "get_tree_path": [vp, ip], "get_fused_stats": [vp, C.POINTER(i64)], "get_sweep_stats": [vp, C.POINTER(i64)], "get_sweep_busy": [vp, C.POINTER(i64)], "get_sweep_spec": [vp, C.POINTER(i64)], "set_test_hook": [vp, i32, i64], "set_hmc_mode": [vp, i32], "get_hmc_mode": [vp, ip],
@@ -790,6 +802,17 @@ class Sampler:
         out = (C.c_double * 4)()
         self._check(self._f("get_nuts_stats")(self._h, out))
         return dict(transitions=int(out[0]), sum_treedepth=int(out[1]), sum_n_leapfrog=int(out[2]), divergent=int(out[3]))
+
+    def set_nuts_helpers(self, n: int, wait: bool = False) -> None:
+        """Run-ahead helper threads of the NUTS transition: 0 none, 1 the backward direction (default), 2 both.  Same chain either way.
+        wait (a test hook, not for use): the sampler's thread waits for a state its helper has not finished instead of computing it itself."""
+        self._check(self._f("set_nuts_helpers")(self._h, int(n) | (16 if wait and n else 0)))
+
+    def get_nuts_runahead(self) -> dict:
+        """Run-ahead counters since creation."""
+        out = (C.c_int64 * 4)()
+        self._check(self._f("get_nuts_runahead")(self._h, out))
+        return dict(taken=int(out[0]), not_ready=int(out[1]), unconsumed=int(out[2]), transitions_without_helper=int(out[3]))
 
     def predict_bart(self, x_test: np.ndarray, offset_test: Optional[np.ndarray] = None) -> np.ndarray:
         """``stan4bart_predictBART(x_test, offset_test)``: BART fit of every kept draw (keep_trees) at new rows, [n_test x samples]."""

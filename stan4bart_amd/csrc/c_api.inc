@@ -188,6 +188,9 @@ int S4B_FN(test_stan_sums)(s4b_sampler* s, int32_t mode, const double* beta, con
 int S4B_FN(get_sweep_busy)(s4b_sampler* s, int64_t* out) { S4B_NEED(s, "get_sweep_busy") S4B_TRY if (!out) throw std::invalid_argument("get_sweep_busy: NULL output pointer"); *out = s->core.dev().sweep_busy(); S4B_CATCH }
 int S4B_FN(get_counters)(s4b_sampler* s, int64_t out[3]) { S4B_NEED(s, "get_counters") S4B_TRY s->core.dev().bind(); s->core.counters(out); S4B_CATCH }
 int S4B_FN(get_nuts_stats)(s4b_sampler* s, double out[4]) { S4B_NEED(s, "get_nuts_stats") S4B_TRY s->core.dev().bind(); s->core.nuts_stats(out); S4B_CATCH }
+int S4B_FN(set_nuts_helpers)(s4b_sampler* s, int32_t n) { S4B_NEED(s, "set_nuts_helpers") S4B_TRY s->core.set_nuts_helpers(n); S4B_CATCH }
+int S4B_FN(get_nuts_runahead)(s4b_sampler* s, int64_t out[4]) { S4B_NEED(s, "get_nuts_runahead") S4B_TRY if (!out) throw std::invalid_argument("get_nuts_runahead: NULL output pointer"); s->core.nuts_runahead(out); S4B_CATCH }
+int S4B_FN(set_host_vector)(int32_t on, int32_t* effective) { S4B_TRY const int v = on < 0 ? (s4b::host_vector_on() ? 1 : 0) : s4b::set_host_vector(on); if (effective) *effective = v; S4B_CATCH }
 int S4B_FN(profile_sweep)(s4b_sampler* s, int32_t n_sweeps, double out[8]) { S4B_NEED(s, "profile_sweep") S4B_TRY s->core.dev().bind(); s->core.profile_sweep(n_sweeps, out); S4B_CATCH }
 int S4B_FN(profile_leapfrog)(s4b_sampler* s, int32_t n_evals, double out[8]) { S4B_NEED(s, "profile_leapfrog") S4B_TRY s->core.dev().bind(); s->core.profile_leapfrog(n_evals, out); S4B_CATCH }
 int S4B_FN(stream_probe)(int32_t device, int64_t n_doubles, int32_t reps, double out[4]) { S4B_TRY S4B_DEV::probe_stream(device, n_doubles, reps, out); S4B_CATCH }

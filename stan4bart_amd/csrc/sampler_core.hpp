@@ -405,7 +405,7 @@ class SamplerCore {
     //      interruptable_sampler.hpp:150,175-176 happen before any BART fit exists)
     if (hmcMode_ == 0) { build_gram(sd); haveGram_ = true; }
     dev_.stan_inputs(/*mode raw y*/ 0, false, cX_.data(), cZ_.data(), &s0_, nullptr);
-    model_->lik = [this](const double* beta, const double* b, double* gX, double* gZ) { return likelihood(beta, b, gX, gZ); };
+    model_->lik = [this](const double* beta, const double* b, double* gX, double* gZ, double* th) { return likelihood(beta, b, gX, gZ, th); };
     NutsControl nc;
     nc.seed = sc->seed; nc.init_r = sc->init_r; nc.skip = sc->skip;
     if (nc.skip <= 0) { nc.skip = (2000 - warmup_) / 1000; if (nc.skip < 1) nc.skip = 1; }
@@ -413,6 +413,9 @@ class SamplerCore {
     nc.init_buffer = sc->adapt_init_buffer; nc.term_buffer = sc->adapt_term_buffer; nc.window = sc->adapt_window;
     nc.stepsize = sc->stepsize; nc.jitter = sc->stepsize_jitter; nc.max_depth = sc->max_treedepth;
     nuts_.reset(new Nuts(*model_, nc, 1, warmup_));
+    // run-ahead helpers of the NUTS transition (stan_host.hpp Nuts::RunAhead): one by default, S4B_NUTS_HELPERS = 0 / 1 / 2 (more: 2, negative: 0)
+    { const char* e = std::getenv("S4B_NUTS_HELPERS"); const int n = e && *e ? std::atoi(e) : 1; nuts_->set_helpers(n < 0 ? 0 : (n > 2 ? 2 : n)); }
+    sync_runahead();
     row_.assign((size_t)(7 + model_->sp.n_constrained), 0.0);
 
     // ---- BART init (reference src/init.cpp:236-273)
@@ -1458,7 +1461,15 @@ class SamplerCore {
     if (mode != 0 && mode != 1) throw std::invalid_argument("hmc_mode must be 0 (sufficient statistics) or 1 (one device evaluation per leapfrog)");
     if (mode == 0 && !haveGram_) throw std::invalid_argument("this sampler was created with hmc_mode 1: it has no Gram matrix to evaluate from sufficient statistics");
     hmcMode_ = mode;
+    sync_runahead();
   }
+  // run-ahead helpers (s4b_set_nuts_helpers / s4b_get_nuts_runahead)
+  void set_nuts_helpers(int n) {
+    live();
+    if (n < 0 || (n & ~16) > 2) throw std::invalid_argument("nuts helpers must be 0 (none), 1 (the backward direction) or 2 (both directions), plus 16 to wait for a helper");
+    if (nuts_) nuts_->set_helpers(n & 3, (n & 16) != 0);
+  }
+  void nuts_runahead(int64_t out[4]) { live(); for (int i = 0; i < 4; ++i) out[i] = 0; if (nuts_) nuts_->runahead_counters(out); }
   // latent mode (s4b_set_latent_mode): 0 = the reference's draw from R's stream, 1 = parallel draw under the chain's Philox key
   static constexpr bool kLatentMode = has_latent_mode<Dev>::value;
   int latent_mode() const { live(); return latMode_; }
@@ -1951,28 +1962,18 @@ class SamplerCore {
     for (int a = 0; a < M; ++a) if (gramPtr_[(size_t)a + 1] < gramPtr_[(size_t)a]) gramPtr_[(size_t)a + 1] = gramPtr_[(size_t)a];
   }
   // ss = e'We, gX = X'We, gZ = Z'We with e = (y - offset) - X beta - Z b (W = I without weights)
-  double likelihood(const double* beta, const double* b, double* gX, double* gZ) {
+  // A helper thread integrates ahead only where a gradient is closed-form host arithmetic over the Gram form: it never reaches the device layer.
+  void sync_runahead() { if (nuts_) nuts_->set_runahead_allowed(model_->has_closed_form() && hmcMode_ == 0 && haveGram_ && model_->gradientCheck == 0); }
+  // (th: the calling thread's work space of K + q + 4 doubles, zeros from K + q on; the Gram form reads members only, so two threads may be in it)
+  double likelihood(const double* beta, const double* b, double* gX, double* gZ, double* th) {
     if (hmcMode_ != 0) return dev_.leapfrog_sums(beta, b, gX, gZ);
     // (hundreds of calls per Gibbs iteration once the chain runs deep NUTS trees: theta = [beta; b] contiguous, no branch per entry;
     // same products in the same order as the two-array form)
     const int M = K_ + q_;
-    if (thetaBuf_.size() < (size_t)M + 4) thetaBuf_.assign((size_t)M + 4, 0.0);
-    double* const th = thetaBuf_.data();
     for (int k = 0; k < K_; ++k) th[k] = beta[k];
     for (int j = 0; j < q_; ++j) th[K_ + j] = b[j];
     if (gramLd_) {
-      const double* const G = gramDense_.data(); const int ld = gramLd_;
-      double ss = s0_;
-      for (int a = 0; a < M; ++a) {
-        const double* const r = G + (size_t)a * ld;
-        double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-        for (int c = 0; c < ld; c += 4) { p0 += r[c] * th[c]; p1 += r[c + 1] * th[c + 1]; p2 += r[c + 2] * th[c + 2]; p3 += r[c + 3] * th[c + 3]; }
-        const double ga = (p0 + p2) + (p1 + p3);
-        const double ca = a < K_ ? cX_[(size_t)a] : cZ_[(size_t)(a - K_)];
-        ss += th[a] * (ga - 2.0 * ca);
-        if (a < K_) gX[a] = ca - ga; else gZ[a - K_] = ca - ga;
-      }
-      return ss;
+      return hostloop::gram_dense(host_vector_on(), gramDense_.data(), gramLd_, M, K_, th, cX_.data(), cZ_.data(), s0_, gX, gZ);
     }
     const int* const ptr = gramPtr_.data(); const int* const col = gramCol_.data(); const double* const g = gram_.data();
     double ss = s0_;
@@ -1995,7 +1996,6 @@ class SamplerCore {
 
   Dev dev_;
   size_t n_ = 0, nTest_ = 0; int P_ = 0, T_ = 0, nc_ = 256, thin_ = 1, K_ = 0, q_ = 0, hmcMode_ = 0; bool haveGram_ = false;
-  std::vector<double> thetaBuf_;
   int warmup_ = 0, verbose_ = 0, refresh_ = 0, offsetType_ = 0; s4b_progress_fn progress_ = nullptr; void* progressUser_ = nullptr; bool keepFits_ = true, hasUserOffset_ = false, binary_ = false;
   std::vector<double> userOffset_;
   s4b_callback_fn callback_ = nullptr; void* callbackUser_ = nullptr;

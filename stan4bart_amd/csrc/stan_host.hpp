@@ -14,17 +14,239 @@
 #define S4B_STAN_HOST_HPP
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <condition_variable>
 #include <cstdint>
+#include <cstdlib>
 #include <functional>
 #include <chrono>
 #include <cstdio>
 #include <limits>
+#include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
+#if defined(__linux__)
+#include <pthread.h>
+#include <sched.h>
+#endif
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+#include <immintrin.h>
+#define S4B_HOST_AVX2 1
+#define S4B_TARGET_AVX2 __attribute__((target("avx2")))
+#endif
+// No fused multiply-add in the host loops of a leapfrog, whatever flags the translation unit is built with (-march=native, -mfma): their
+// scalar and AVX2 forms, and the two threads of a run-ahead, must round a product and the sum it enters separately.  clang takes the pragma at
+// the head of a function body (at file scope it would reach the device code of a HIP translation unit), gcc the function attribute.
+#if defined(__clang__)
+#define S4B_NO_CONTRACT
+#define S4B_NO_CONTRACT_BODY _Pragma("clang fp contract(off)")
+#elif defined(__GNUC__)
+#define S4B_NO_CONTRACT __attribute__((optimize("fp-contract=off")))
+#define S4B_NO_CONTRACT_BODY
+#else
+#define S4B_NO_CONTRACT
+#define S4B_NO_CONTRACT_BODY
+#endif
 
 namespace s4b {
+
+// ---------------------------------------------------------------- host loops of a leapfrog, scalar and four lanes wide
+// Once the chain runs deep NUTS trees the Stan block's cost in hmc_mode 0 is a thousand leapfrogs of O(D) host arithmetic per Gibbs
+// iteration.  The loops below are that arithmetic.  Each has a scalar form (the definition) and an AVX2 form chosen at run time; the
+// translation unit is built without any -m flag, the AVX2 forms are `target("avx2")` functions.  That target has no fused multiply-add, so
+// a product and the sum it enters are rounded separately in both forms, and every AVX2 form performs the scalar form's operations on the
+// same operands in the same order per result: element-wise loops lane by lane, the four partial sums of a Gram row as the four lanes of
+// one register, the six dot products of a merge as six lanes that each add their terms from element 0 upwards.  The results are the
+// scalar form's bit for bit (tests/test_nuts_runahead.py runs whole chains both ways).
+inline bool host_vector_supported() {
+#ifdef S4B_HOST_AVX2
+  return __builtin_cpu_supports("avx2") != 0;
+#else
+  return false;
+#endif
+}
+// process-wide switch: on where the CPU has AVX2, unless S4B_HOST_VECTOR=0; s4b_set_host_vector changes it (a test forces both forms)
+inline std::atomic<int>& host_vector_flag() {
+  static std::atomic<int> f{[] { const char* e = std::getenv("S4B_HOST_VECTOR"); return (host_vector_supported() && !(e && std::atoi(e) == 0)) ? 1 : 0; }()};
+  return f;
+}
+inline bool host_vector_on() { return host_vector_flag().load(std::memory_order_relaxed) != 0; }
+inline int set_host_vector(int on) { const int v = (on && host_vector_supported()) ? 1 : 0; host_vector_flag().store(v, std::memory_order_relaxed); return v; }
+inline void cpu_pause() {
+#ifdef S4B_HOST_AVX2
+  _mm_pause();
+#else
+  std::this_thread::yield();
+#endif
+}
+
+namespace hostloop {
+// ss = s0 + th'(G th - 2c), gX / gZ = c - G th for the dense Gram matrix (rows padded with zeros to ld, a multiple of four; th holds M
+// entries and zeros up to ld).  A row's product is summed into four accumulators combined as (p0 + p2) + (p1 + p3).
+S4B_NO_CONTRACT inline double gram_dense_scalar(const double* G, int ld, int M, int K, const double* th, const double* cX, const double* cZ, double s0, double* gX, double* gZ) {
+  S4B_NO_CONTRACT_BODY
+  double ss = s0;
+  for (int a = 0; a < M; ++a) {
+    const double* const r = G + (size_t)a * ld;
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
+    for (int c = 0; c < ld; c += 4) { p0 += r[c] * th[c]; p1 += r[c + 1] * th[c + 1]; p2 += r[c + 2] * th[c + 2]; p3 += r[c + 3] * th[c + 3]; }
+    const double ga = (p0 + p2) + (p1 + p3);
+    const double ca = a < K ? cX[a] : cZ[a - K];
+    ss += th[a] * (ga - 2.0 * ca);
+    if (a < K) gX[a] = ca - ga; else gZ[a - K] = ca - ga;
+  }
+  return ss;
+}
+// first half of a leapfrog: p -= (e/2) g, q += e (M^-1 p)
+S4B_NO_CONTRACT inline void kick_drift_scalar(int D, double e, double he, double* __restrict__ p, double* __restrict__ q, const double* __restrict__ g, const double* __restrict__ im) {
+  S4B_NO_CONTRACT_BODY
+  for (int i = 0; i < D; ++i) { const double pi = p[i] - he * g[i]; p[i] = pi; q[i] += e * (im[i] * pi); }
+}
+// end of a leaf: (Kick: the second half kick p -= (e/2) g, then) the momentum's sharp, the kinetic sum from element 0 upwards, and the
+// subtree's one-point summaries
+template <bool Kick>
+S4B_NO_CONTRACT inline double leaf_finish_scalar(int D, double he, double* __restrict__ p, const double* __restrict__ g, const double* __restrict__ im, double* __restrict__ sb,
+                                 double* __restrict__ se, double* __restrict__ rh, double* __restrict__ pb, double* __restrict__ pe) {
+  S4B_NO_CONTRACT_BODY
+  double kin = 0.0;
+  for (int i = 0; i < D; ++i) {
+    const double pi = Kick ? p[i] - he * g[i] : p[i], sh = im[i] * pi;
+    p[i] = pi; kin += pi * sh; sb[i] = sh; se[i] = sh; rh[i] += pi; pb[i] = pi; pe[i] = pi;
+  }
+  return kin;
+}
+// merge of two subtrees: rho += rho_init + rho_final, and the six dot products of the three U-turn criteria, out = {a1, b1, a2, b2, a3, b3}
+S4B_NO_CONTRACT inline void merge_scalar(int D, const double* __restrict__ ri, const double* __restrict__ rf, const double* __restrict__ pfb, const double* __restrict__ pie,
+                         const double* __restrict__ sb, const double* __restrict__ se, const double* __restrict__ sfb, const double* __restrict__ sie,
+                         double* __restrict__ rh, double out[6]) {
+  S4B_NO_CONTRACT_BODY
+  double a1 = 0, b1 = 0, a2 = 0, b2 = 0, a3 = 0, b3 = 0;
+  for (int i = 0; i < D; ++i) {
+    const double rs = ri[i] + rf[i], t2 = ri[i] + pfb[i], t3 = rf[i] + pie[i];
+    rh[i] += rs;
+    a1 += se[i] * rs; b1 += sb[i] * rs;
+    a2 += sfb[i] * t2; b2 += sb[i] * t2;
+    a3 += se[i] * t3; b3 += sie[i] * t3;
+  }
+  out[0] = a1; out[1] = b1; out[2] = a2; out[3] = b2; out[4] = a3; out[5] = b3;
+}
+#ifdef S4B_HOST_AVX2
+S4B_TARGET_AVX2 S4B_NO_CONTRACT inline double gram_dense_avx2(const double* G, int ld, int M, int K, const double* th, const double* cX, const double* cZ, double s0, double* gX, double* gZ) {
+  S4B_NO_CONTRACT_BODY
+  double ss = s0;
+  for (int a = 0; a < M; ++a) {
+    const double* const r = G + (size_t)a * ld;
+    __m256d acc = _mm256_setzero_pd();                              // lanes p0 p1 p2 p3
+    for (int c = 0; c < ld; c += 4) acc = _mm256_add_pd(acc, _mm256_mul_pd(_mm256_loadu_pd(r + c), _mm256_loadu_pd(th + c)));
+    const __m128d s = _mm_add_pd(_mm256_castpd256_pd128(acc), _mm256_extractf128_pd(acc, 1));   // p0 + p2, p1 + p3
+    const double ga = _mm_cvtsd_f64(_mm_add_sd(s, _mm_unpackhi_pd(s, s)));
+    const double ca = a < K ? cX[a] : cZ[a - K];
+    ss += th[a] * (ga - 2.0 * ca);
+    if (a < K) gX[a] = ca - ga; else gZ[a - K] = ca - ga;
+  }
+  return ss;
+}
+S4B_TARGET_AVX2 S4B_NO_CONTRACT inline void kick_drift_avx2(int D, double e, double he, double* __restrict__ p, double* __restrict__ q, const double* __restrict__ g, const double* __restrict__ im) {
+  S4B_NO_CONTRACT_BODY
+  const __m256d ve = _mm256_set1_pd(e), vhe = _mm256_set1_pd(he);
+  int i = 0;
+  for (; i + 4 <= D; i += 4) {
+    const __m256d pi = _mm256_sub_pd(_mm256_loadu_pd(p + i), _mm256_mul_pd(vhe, _mm256_loadu_pd(g + i)));
+    _mm256_storeu_pd(p + i, pi);
+    _mm256_storeu_pd(q + i, _mm256_add_pd(_mm256_loadu_pd(q + i), _mm256_mul_pd(ve, _mm256_mul_pd(_mm256_loadu_pd(im + i), pi))));
+  }
+  for (; i < D; ++i) { const double pi = p[i] - he * g[i]; p[i] = pi; q[i] += e * (im[i] * pi); }
+}
+template <bool Kick>
+S4B_TARGET_AVX2 S4B_NO_CONTRACT inline double leaf_finish_avx2(int D, double he, double* __restrict__ p, const double* __restrict__ g, const double* __restrict__ im, double* __restrict__ sb,
+                                               double* __restrict__ se, double* __restrict__ rh, double* __restrict__ pb, double* __restrict__ pe) {
+  S4B_NO_CONTRACT_BODY
+  const __m256d vhe = _mm256_set1_pd(he);
+  double kin = 0.0;
+  int i = 0;
+  for (; i + 4 <= D; i += 4) {
+    __m256d pi = _mm256_loadu_pd(p + i);
+    if (Kick) pi = _mm256_sub_pd(pi, _mm256_mul_pd(vhe, _mm256_loadu_pd(g + i)));
+    const __m256d sh = _mm256_mul_pd(_mm256_loadu_pd(im + i), pi);
+    alignas(32) double t[4];
+    _mm256_store_pd(t, _mm256_mul_pd(pi, sh));
+    kin += t[0]; kin += t[1]; kin += t[2]; kin += t[3];             // (the kinetic sum keeps its order)
+    _mm256_storeu_pd(p + i, pi); _mm256_storeu_pd(sb + i, sh); _mm256_storeu_pd(se + i, sh);
+    _mm256_storeu_pd(rh + i, _mm256_add_pd(_mm256_loadu_pd(rh + i), pi)); _mm256_storeu_pd(pb + i, pi); _mm256_storeu_pd(pe + i, pi);
+  }
+  for (; i < D; ++i) {
+    const double pi = Kick ? p[i] - he * g[i] : p[i], sh = im[i] * pi;
+    p[i] = pi; kin += pi * sh; sb[i] = sh; se[i] = sh; rh[i] += pi; pb[i] = pi; pe[i] = pi;
+  }
+  return kin;
+}
+// four elements at a time: the six products along i, transposed so that one register holds {a1, b1, a2, b2} of ONE element and is added to
+// the accumulators element after element; {a3, b3} likewise in a two-lane register
+S4B_TARGET_AVX2 S4B_NO_CONTRACT inline void merge_avx2(int D, const double* __restrict__ ri, const double* __restrict__ rf, const double* __restrict__ pfb, const double* __restrict__ pie,
+                                       const double* __restrict__ sb, const double* __restrict__ se, const double* __restrict__ sfb, const double* __restrict__ sie,
+                                       double* __restrict__ rh, double out[6]) {
+  S4B_NO_CONTRACT_BODY
+  __m256d acc4 = _mm256_setzero_pd(); __m128d acc2 = _mm_setzero_pd();
+  int i = 0;
+  for (; i + 4 <= D; i += 4) {
+    const __m256d vri = _mm256_loadu_pd(ri + i), vrf = _mm256_loadu_pd(rf + i), vsb = _mm256_loadu_pd(sb + i), vse = _mm256_loadu_pd(se + i);
+    const __m256d rs = _mm256_add_pd(vri, vrf), t2 = _mm256_add_pd(vri, _mm256_loadu_pd(pfb + i)), t3 = _mm256_add_pd(vrf, _mm256_loadu_pd(pie + i));
+    _mm256_storeu_pd(rh + i, _mm256_add_pd(_mm256_loadu_pd(rh + i), rs));
+    const __m256d pa1 = _mm256_mul_pd(vse, rs), pb1 = _mm256_mul_pd(vsb, rs), pa2 = _mm256_mul_pd(_mm256_loadu_pd(sfb + i), t2), pb2 = _mm256_mul_pd(vsb, t2);
+    const __m256d pa3 = _mm256_mul_pd(vse, t3), pb3 = _mm256_mul_pd(_mm256_loadu_pd(sie + i), t3);
+    const __m256d u0 = _mm256_unpacklo_pd(pa1, pb1), u1 = _mm256_unpackhi_pd(pa1, pb1), u2 = _mm256_unpacklo_pd(pa2, pb2), u3 = _mm256_unpackhi_pd(pa2, pb2);
+    acc4 = _mm256_add_pd(acc4, _mm256_permute2f128_pd(u0, u2, 0x20));   // element i
+    acc4 = _mm256_add_pd(acc4, _mm256_permute2f128_pd(u1, u3, 0x20));   // element i + 1
+    acc4 = _mm256_add_pd(acc4, _mm256_permute2f128_pd(u0, u2, 0x31));   // element i + 2
+    acc4 = _mm256_add_pd(acc4, _mm256_permute2f128_pd(u1, u3, 0x31));   // element i + 3
+    const __m256d w0 = _mm256_unpacklo_pd(pa3, pb3), w1 = _mm256_unpackhi_pd(pa3, pb3);
+    acc2 = _mm_add_pd(acc2, _mm256_castpd256_pd128(w0)); acc2 = _mm_add_pd(acc2, _mm256_castpd256_pd128(w1));
+    acc2 = _mm_add_pd(acc2, _mm256_extractf128_pd(w0, 1)); acc2 = _mm_add_pd(acc2, _mm256_extractf128_pd(w1, 1));
+  }
+  alignas(32) double t[4]; alignas(16) double u[2];
+  _mm256_store_pd(t, acc4); _mm_store_pd(u, acc2);
+  double a1 = t[0], b1 = t[1], a2 = t[2], b2 = t[3], a3 = u[0], b3 = u[1];
+  for (; i < D; ++i) {
+    const double rs = ri[i] + rf[i], t2 = ri[i] + pfb[i], t3 = rf[i] + pie[i];
+    rh[i] += rs;
+    a1 += se[i] * rs; b1 += sb[i] * rs;
+    a2 += sfb[i] * t2; b2 += sb[i] * t2;
+    a3 += se[i] * t3; b3 += sie[i] * t3;
+  }
+  out[0] = a1; out[1] = b1; out[2] = a2; out[3] = b2; out[4] = a3; out[5] = b3;
+}
+#endif
+inline double gram_dense(bool vec, const double* G, int ld, int M, int K, const double* th, const double* cX, const double* cZ, double s0, double* gX, double* gZ) {
+#ifdef S4B_HOST_AVX2
+  if (vec) return gram_dense_avx2(G, ld, M, K, th, cX, cZ, s0, gX, gZ);
+#endif
+  (void)vec; return gram_dense_scalar(G, ld, M, K, th, cX, cZ, s0, gX, gZ);
+}
+inline void kick_drift(bool vec, int D, double e, double he, double* p, double* q, const double* g, const double* im) {
+#ifdef S4B_HOST_AVX2
+  if (vec) { kick_drift_avx2(D, e, he, p, q, g, im); return; }
+#endif
+  (void)vec; kick_drift_scalar(D, e, he, p, q, g, im);
+}
+template <bool Kick>
+inline double leaf_finish(bool vec, int D, double he, double* p, const double* g, const double* im, double* sb, double* se, double* rh, double* pb, double* pe) {
+#ifdef S4B_HOST_AVX2
+  if (vec) return leaf_finish_avx2<Kick>(D, he, p, g, im, sb, se, rh, pb, pe);
+#endif
+  (void)vec; return leaf_finish_scalar<Kick>(D, he, p, g, im, sb, se, rh, pb, pe);
+}
+inline void merge(bool vec, int D, const double* ri, const double* rf, const double* pfb, const double* pie, const double* sb, const double* se, const double* sfb,
+                  const double* sie, double* rh, double out[6]) {
+#ifdef S4B_HOST_AVX2
+  if (vec) { merge_avx2(D, ri, rf, pfb, pie, sb, se, sfb, sie, rh, out); return; }
+#endif
+  (void)vec; merge_scalar(D, ri, rf, pfb, pie, sb, se, sfb, sie, rh, out);
+}
+}  // namespace hostloop
 
 // ---------------------------------------------------------------- reverse-mode tape
 // The model's control flow depends on the data description only (StanSpec), never on parameter values: the tape of a gradient has
@@ -161,16 +383,30 @@ struct StanSpec {
 
 // O(N) part: given beta, b, sigma returns ss = sum (y - offset - X beta - Z b)^2 and fills
 // gX = X'e, gZ = Z'e (e the residual).  Implemented by the device layer.
-typedef std::function<double(const double* beta, const double* b, double* gX, double* gZ)> Likelihood;
+// `theta` is the caller's work space of K + q + 4 doubles (zeros from K + q on, kept so): the evaluation itself holds no state, so that two
+// threads with a work space each may evaluate at the same time.
+typedef std::function<double(const double* beta, const double* b, double* gX, double* gZ, double* theta)> Likelihood;
 
 class HostModel {
  public:
   StanSpec sp;
   Likelihood lik;
-  long gradEvals = 0;
-  explicit HostModel(const StanSpec& s) : sp(s) { sp.finish(); plan_closed_form(); }
+  // (a line of its own: the sampler's thread counts here while a run-ahead helper reads the model's description next to it)
+  alignas(64) long gradEvals = 0;
+  explicit HostModel(const StanSpec& s) : sp(s) { sp.finish(); plan_closed_form(); size_scratch(scratch_); }
+  // Work space of one gradient evaluation.  The model keeps one for its own thread; a run-ahead helper of the sampler (Nuts::RunAhead)
+  // brings its own, and the closed-form gradient then is the same compiled function on either thread: same arithmetic, same order.
+  struct CfWork { double tau, A, rho, e, z0, z1, S, pi0, pi1, trace, sd1, T21, sq; };   // forward values of one term, kept for the backward pass
+  struct Scratch { std::vector<double> beta, b, gX, gZ, th, theta; std::vector<CfWork> work; };
+  void size_scratch(Scratch& s) const {
+    s.beta.assign((size_t)sp.K + 1, 0.0); s.b.assign((size_t)sp.q + 1, 0.0); s.gX.assign((size_t)sp.K + 1, 0.0); s.gZ.assign((size_t)sp.q + 1, 0.0);
+    s.th.assign((size_t)(3 * sp.t + 1), 0.0); s.theta.assign((size_t)(sp.K + sp.q) + 4, 0.0); s.work.assign((size_t)sp.t + 1, CfWork{});
+  }
+  // log density and gradient in closed form, for a thread that brings its own work space (has_closed_form() only; counts nothing, throws nothing
+  // of its own; non-finite values come out as they are)
+  double closed_form_with(const double* q, double* g, Scratch& s) const { return closed_form_grad(q, g, s); }
   // (test hook) 0: the closed-form gradient where it applies (default); 1: the tape everywhere; 2: both, compared (throws on a difference)
-  int gradientCheck = 0;
+  alignas(64) int gradientCheck = 0;
 
   struct Fwd { TV sigma; std::vector<TV> beta, b, theta_L, constrained; TV lp; bool wantConstrained = true; };
 
@@ -318,7 +554,7 @@ class HostModel {
     if (closedForm_ && gradientCheck != 1) {
       ++gradEvals;
       grad.resize((size_t)sp.D);
-      const double lp = closed_form_grad(qv.data(), grad.data());
+      const double lp = closed_form_grad(qv.data(), grad.data(), scratch_);
       if (gradientCheck == 2) {
         std::vector<double> g2; const double lp2 = tape_grad(qv, g2); --gradEvals;
         // (far outside the typical set — a diverging trajectory — components of 1e9 are differences of terms of 1e17: the two
@@ -357,7 +593,7 @@ class HostModel {
     for (int k = 0; k < sp.K; ++k) beta[(size_t)k] = F.beta[(size_t)k].v();
     for (int j = 0; j < sp.q; ++j) b[(size_t)j] = F.b[(size_t)j].v();
     double sigma = F.sigma.v();
-    double ss = lik(beta.data(), b.data(), gX.data(), gZ.data());
+    double ss = lik(beta.data(), b.data(), gX.data(), gZ.data(), scratch_.theta.data());
     double s2 = sigma * sigma, N = (double)sp.N;
     double ll = -0.5 * ss / s2 - N * std::log(sigma) - N * 0.91893853320467274178;
     tape_.adj.assign(tape_.ops.size(), 0.0);
@@ -404,13 +640,11 @@ class HostModel {
   // without tape nodes.  Everything else (hs / laplace / lasso / product_normal / student_t coefficients, p_i > 2) stays on the tape;
   // tests/test_priors.py and gradientCheck = 2 compare the two.
   struct CfTerm { int p, l, zb0, rho, zeta, tau; double scale, betaA, lbeta, delta0, delta1, lgDelta0, lgDelta1, shape, lgShape; };
-  struct CfWork { double tau, A, rho, e, z0, z1, S, pi0, pi1, trace, sd1, T21, sq; };   // forward values of one term, kept for the backward pass
-  std::vector<CfWork> cfWork_;
+  Scratch scratch_;
   bool closedForm_ = false;
   std::vector<CfTerm> cfTerms_;
   int cfRho0_ = 0, cfZeta0_ = 0, cfTau0_ = 0, cfAux_ = 0;
   double cfAuxConst_ = 0;
-  std::vector<double> cfBeta_, cfB_, cfGX_, cfGZ_, cfTh_;
   void plan_closed_form() {
     closedForm_ = false;
     if (sp.prior_dist > 1 || sp.hs || sp.n_mix || sp.n_lambda || sp.len_z_T) return;
@@ -436,11 +670,9 @@ class HostModel {
       const double nu = sp.prior_df_for_aux;
       cfAuxConst_ = lg((nu + 1.0) / 2.0) - lg(nu / 2.0) - 0.5 * std::log(nu * M_PI);
     }
-    cfBeta_.assign((size_t)sp.K + 1, 0.0); cfB_.assign((size_t)sp.q + 1, 0.0); cfGX_.assign((size_t)sp.K + 1, 0.0); cfGZ_.assign((size_t)sp.q + 1, 0.0);
-    cfTh_.assign((size_t)(3 * sp.t + 1), 0.0); cfWork_.assign((size_t)sp.t + 1, CfWork{});
     closedForm_ = true;
   }
-  double closed_form_grad(const double* q, double* g) {
+  __attribute__((noinline)) double closed_form_grad(const double* q, double* g, Scratch& sc) const {
     const double HALF_LOG_2PI = 0.91893853320467274178, LOG_HALF = -0.693147180559945286;
     const int K = sp.K, nq = sp.q, t = sp.t;
     double lp = 0.0;
@@ -452,14 +684,14 @@ class HostModel {
       else { aux = u * sp.prior_scale_for_aux; dAuxDu = sp.prior_scale_for_aux; if (sp.prior_dist_for_aux <= 2) aux += sp.prior_mean_for_aux; }
     }
     // ---- coefficients
-    double* const beta = cfBeta_.data(); double* const b = cfB_.data();
+    double* const beta = sc.beta.data(); double* const b = sc.b.data();
     if (sp.prior_dist == 0) for (int k = 0; k < K; ++k) beta[k] = q[k];
     else for (int k = 0; k < K; ++k) { beta[k] = q[k] * sp.prior_scale[(size_t)k] + sp.prior_mean[(size_t)k]; lp += -0.5 * q[k] * q[k] - HALF_LOG_2PI; }
     // ---- theta_L, b (T = [[T00, 0], [T10, T11]] per term with two coefficients)
-    double* const th = cfTh_.data();     // per term: T00 (or theta), T10, T11
+    double* const th = sc.th.data();     // per term: T00 (or theta), T10, T11
     for (int i = 0; i < t; ++i) {
       const CfTerm& c = cfTerms_[(size_t)i];
-      CfWork& w = cfWork_[(size_t)i];
+      CfWork& w = sc.work[(size_t)i];
       const double tau = std::exp(q[c.tau]); lp += q[c.tau];
       const double A = tau * c.scale * aux;
       w.tau = tau; w.A = A;
@@ -498,10 +730,10 @@ class HostModel {
       } else { lp -= u; dLpDu = -1.0; }
     }
     // ---- the O(N) part (device kernels or the Gram form)
-    double* const gX = cfGX_.data(); double* const gZ = cfGZ_.data();
+    double* const gX = sc.gX.data(); double* const gZ = sc.gZ.data();
     for (int k = 0; k < K; ++k) gX[k] = 0.0;
     for (int j = 0; j < nq; ++j) gZ[j] = 0.0;
-    const double ss = lik(beta, b, gX, gZ);
+    const double ss = lik(beta, b, gX, gZ, sc.theta.data());
     const double s2 = aux * aux, N = (double)sp.N, is2 = 1.0 / s2;
     const double ll = -0.5 * ss / s2 - N * std::log(aux) - N * HALF_LOG_2PI;
     double dAux = ss / (s2 * aux) - N / aux;
@@ -511,7 +743,7 @@ class HostModel {
     for (int i = 0; i < t; ++i) {
       const CfTerm& c = cfTerms_[(size_t)i];
       const double* zb = q + c.zb0; const double* gb = gZ + (c.zb0 - K); double* gz = g + c.zb0;
-      const CfWork& w = cfWork_[(size_t)i];
+      const CfWork& w = sc.work[(size_t)i];
       const double tau = w.tau, A = w.A;
       double dA = 0.0;
       if (c.p == 1) {
@@ -709,10 +941,208 @@ struct NutsControl {
   double stepsize = 1, jitter = 0; int max_depth = 10;
 };
 
+// Helper threads of all samplers of the process: at most 8 (a sampler that gets none integrates inline).  The number is fixed, not read
+// off the machine: what a job may use is usually far less than what the machine reports.
+inline std::atomic<int>& runahead_budget() { static std::atomic<int> b{8}; return b; }
+inline bool runahead_budget_take() {
+  int v = runahead_budget().load(std::memory_order_relaxed);
+  while (v > 0) if (runahead_budget().compare_exchange_weak(v, v - 1, std::memory_order_relaxed)) return true;
+  return false;
+}
+inline void runahead_budget_give() { runahead_budget().fetch_add(1, std::memory_order_relaxed); }
+
+// Where a helper runs decides what a hand-over costs: a finished state is seven cache lines that cross from the helper's core to the sampler's.
+// Between cores under one last-level cache that is a few tens of nanoseconds, hidden behind the tree builder's own work; between cores of
+// different cache domains (the chiplets of a large server CPU) it costs as much as the leapfrog it saves.  So a helper is kept on the cores that
+// share the last-level cache of the core the sampler's thread runs on, without that core's own hardware threads, and within the CPUs the
+// process may use.  Linux only (the topology is read from sysfs, once per CPU); anywhere else, or where the files are missing, a helper runs
+// wherever the scheduler puts it.
+#if defined(__linux__)
+struct CpuNeighbours {
+  // CPUs of a sysfs list file ("0-7,128-135"); false if the file cannot be read
+  static bool read_list(const char* fmt, int cpu, cpu_set_t* out) {
+    char path[128]; std::snprintf(path, sizeof path, fmt, cpu);
+    std::FILE* f = std::fopen(path, "r");
+    if (!f) return false;
+    CPU_ZERO(out);
+    int a, b; bool any = false;
+    while (std::fscanf(f, "%d", &a) == 1) {
+      b = a;
+      int ch = std::fgetc(f);
+      if (ch == '-') { if (std::fscanf(f, "%d", &b) != 1) break; ch = std::fgetc(f); }
+      for (int c = a; c <= b && c < CPU_SETSIZE; ++c) if (c >= 0) { CPU_SET(c, out); any = true; }
+      if (ch != ',') break;
+    }
+    std::fclose(f);
+    return any;
+  }
+  // Where a helper of a thread on `cpu` should run.  PLACE: on the CPUs of *out (same last-level cache, another core, allowed to the thread);
+  // ANYWHERE: no advice (no topology to read, or no such core: the scheduler decides); NOWHERE: the thread may use no core but its own (it is
+  // bound to one core, as one-core-per-rank launchers do) — a helper would only take turns with it on that core, so the sampler runs without.
+  // *domain: the CPUs under the last-level cache of `cpu` (the advice holds while the thread stays on them).
+  enum Advice { PLACE, ANYWHERE, NOWHERE };
+  static Advice helper_set(int cpu, cpu_set_t* out, cpu_set_t* domain) {
+    cpu_set_t l3, smt, allowed;
+    CPU_ZERO(domain); CPU_ZERO(out);
+    if (cpu < 0 || cpu >= CPU_SETSIZE) return ANYWHERE;
+    CPU_SET(cpu, domain);
+    if (sched_getaffinity(0, sizeof allowed, &allowed) != 0) return ANYWHERE;
+    if (!read_list("/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", cpu, &smt)) { CPU_ZERO(&smt); CPU_SET(cpu, &smt); }
+    int others = 0;
+    for (int c = 0; c < CPU_SETSIZE; ++c) if (CPU_ISSET(c, &allowed) && !CPU_ISSET(c, &smt)) ++others;
+    if (others == 0) return NOWHERE;
+    if (!read_list("/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", cpu, &l3)) return ANYWHERE;
+    *domain = l3; CPU_SET(cpu, domain);
+    int n = 0;
+    for (int c = 0; c < CPU_SETSIZE; ++c) if (CPU_ISSET(c, &l3) && CPU_ISSET(c, &allowed) && !CPU_ISSET(c, &smt)) { CPU_SET(c, out); ++n; }
+    if (n > 0) return PLACE;
+    *out = allowed;           // (another cache domain is all there is: anywhere the thread itself may run)
+    return PLACE;
+  }
+};
+#endif
+
 class Nuts {
  public:
   typedef std::vector<double> V;
   struct Pt { V q, p, g; double Vv = 0; };
+
+  // ---- run-ahead integrator
+  // The leapfrog states at +1, +2, ... and -1, -2, ... steps from a transition's start are a function of the start point, the momentum
+  // draw, the step size and the metric alone; the order of the doublings only decides WHEN the tree builder consumes each of them, and a
+  // subtree in one direction continues exactly where the previous subtree in that direction stopped.  A RunAhead is one thread that
+  // integrates one direction of the current transition into an array of 2^max_depth states {q, p, V, g} and publishes how many are
+  // finished; the leaf of subtree() takes the next state from it if it is finished (and does the step itself if not).  Everything after the gradient (kinetic energy,
+  // sharp, rho, the weights, the divergence test, the proposal) stays on the sampler's thread.  The helper evaluates the closed-form
+  // gradient over the Gram form with a work space of its own — the function the sampler's thread would run, on the same inputs — draws
+  // nothing, touches no device, and sleeps on a condition variable between transitions.
+  class RunAhead {
+   public:
+    // (a state's slot is a whole number of cache lines, so that the slot the helper writes shares no line with the one the sampler reads)
+    RunAhead(const HostModel& m, int D, size_t cap) : model_(m), D_(D), cap_(cap), stride_(((size_t)3 * D + 1 + 7) & ~(size_t)7) {
+      th_ = std::thread([this] { thread_main(); });
+      std::unique_lock<std::mutex> lk(m_);
+      cv_.wait(lk, [this] { return phase_ != INIT; });
+      if (phase_ == FAILED) { lk.unlock(); th_.join(); throw std::bad_alloc(); }
+    }
+    ~RunAhead() {
+      finish();
+      { std::lock_guard<std::mutex> lk(m_); phase_ = QUIT; }
+      cv_.notify_one();
+      th_.join();
+    }
+    RunAhead(const RunAhead&) = delete; RunAhead& operator=(const RunAhead&) = delete;
+    // (sampler's thread) keep the helper next to `cpu`, the CPU the sampler's thread is on (see CpuNeighbours)
+#if defined(__linux__)
+    void place_on(const cpu_set_t& set) { pthread_setaffinity_np(th_.native_handle(), sizeof set, &set); }
+#endif
+    // (sampler's thread) hand over the start of a transition and wake the helper; e is the signed step size of the helper's direction
+    void start(const Pt& z, double e, const V& inv_metric, bool vec) {
+      {
+        std::lock_guard<std::mutex> lk(m_);    // (the helper is parked: finish() ended the previous transition)
+        q_ = z.q; p_ = z.p; g_ = z.g; im_ = inv_metric; e_ = e; vec_ = vec;
+        taken_ = 0; count_.store(0, std::memory_order_relaxed); stop_.store(0, std::memory_order_relaxed); busy_.store(1, std::memory_order_relaxed);
+        phase_ = POSTED;
+      }
+      cv_.notify_one();
+    }
+    // (sampler's thread) end of the transition: the helper stops after the step it is in and parks; returns the states computed and not consumed
+    int64_t finish() {
+      {
+        std::lock_guard<std::mutex> lk(m_);
+        if (phase_ == POSTED) { phase_ = IDLE; busy_.store(0, std::memory_order_relaxed); }   // never picked up
+      }
+      stop_.store(1, std::memory_order_relaxed);
+      for (unsigned spins = 0; busy_.load(std::memory_order_acquire); ++spins) { if (spins < 4096) cpu_pause(); else std::this_thread::yield(); }
+      const int64_t done = count_.load(std::memory_order_relaxed), left = done > taken_ ? done - taken_ : 0;
+      count_.store(0, std::memory_order_relaxed); taken_ = 0;
+      return left;
+    }
+    // (sampler's thread) state k of the helper's direction, {q[D], p[D], V, g[D]} — the state k + 1 steps from the transition's start — if the
+    // helper has finished it; otherwise NULL, or with `wait` the state once it is there.  The tree builder reads q, p and V of a state it takes
+    // (the next step in this direction normally is the helper's work too); gradient_of(k) is there for the step it then does itself.
+    const double* take(int64_t k, bool wait, bool& waited) {
+      if ((size_t)k >= cap_) throw std::logic_error("NUTS run-ahead: more leapfrogs in one direction than 2^max_depth");
+      waited = false;
+      int64_t c = count_.load(std::memory_order_acquire);
+      if (c <= k) {
+        if (!wait) return nullptr;
+        waited = true;
+        for (unsigned spins = 0; (c = count_.load(std::memory_order_acquire)) <= k; ++spins) { if (spins < 4096) cpu_pause(); else std::this_thread::yield(); }
+      }
+      if (k + 1 > taken_) taken_ = k + 1;
+      const double* const s = states_ + (size_t)k * stride_;
+      if (c > k + 1) {        // the state after this one is finished too: bring it over from the helper's cache while the tree is built
+        const char* const nx = reinterpret_cast<const char*>(s + stride_);
+        for (size_t b = 0; b < ((size_t)2 * D_ + 1) * sizeof(double); b += 64) __builtin_prefetch(nx + b, 0, 3);
+      }
+      return s;
+    }
+    const double* gradient_of(int64_t k) const { return states_ + (size_t)k * stride_ + 2 * (size_t)D_ + 1; }    // (of a state that was taken)
+   private:
+    enum { INIT = 0, FAILED, IDLE, POSTED, RUNNING, QUIT };
+    void thread_main() {
+      // The helper allocates what it writes itself, from its own thread: its buffers then come from its own allocation arena and share no
+      // cache line with anything the sampler's thread writes.
+      bool ok = true;
+      try {
+        model_.size_scratch(scratch_);
+        q_.assign((size_t)D_, 0.0); p_.assign((size_t)D_, 0.0); g_.assign((size_t)D_, 0.0); im_.assign((size_t)D_, 0.0);
+        raw_.reset(new double[cap_ * stride_ + 8]);
+        states_ = raw_.get();
+        while ((reinterpret_cast<uintptr_t>(states_) & 63u) != 0) ++states_;
+      } catch (...) { ok = false; }
+      std::unique_lock<std::mutex> lk(m_);
+      phase_ = ok ? IDLE : FAILED;
+      cv_.notify_all();
+      if (!ok) return;
+      for (;;) {
+        cv_.wait(lk, [this] { return phase_ == POSTED || phase_ == QUIT; });
+        if (phase_ == QUIT) return;
+        phase_ = RUNNING;
+        lk.unlock();
+        integrate();
+        lk.lock();
+        phase_ = IDLE;
+        busy_.store(0, std::memory_order_release);
+      }
+    }
+    S4B_NO_CONTRACT void integrate() {
+      S4B_NO_CONTRACT_BODY
+      const int D = D_; const double e = e_, he = 0.5 * e_;
+      double* const q = q_.data(); double* const p = p_.data(); double* const g = g_.data();
+      for (size_t k = 0; k < cap_; ++k) {
+        if (stop_.load(std::memory_order_relaxed)) return;
+        hostloop::kick_drift(vec_, D, e, he, p, q, g, im_.data());
+        const double Vv = -model_.closed_form_with(q, g, scratch_);
+        for (int i = 0; i < D; ++i) g[i] = -g[i];
+        for (int i = 0; i < D; ++i) p[i] -= he * g[i];
+        double* const s = states_ + k * stride_;
+        std::copy(q, q + D, s); std::copy(p, p + D, s + D); s[2 * (size_t)D] = Vv; std::copy(g, g + D, s + 2 * (size_t)D + 1);
+        count_.store((int64_t)k + 1, std::memory_order_release);
+      }
+    }
+    // what the helper reads while it integrates; the sampler's thread writes it in start() only, while the helper is parked
+    const HostModel& model_; const int D_; const size_t cap_, stride_;
+    HostModel::Scratch scratch_;
+    V q_, p_, g_, im_; double e_ = 0; bool vec_ = false;
+    std::unique_ptr<double[]> raw_; double* states_ = nullptr;
+    std::thread th_; std::mutex m_; std::condition_variable cv_; int phase_ = INIT;
+    // a cache line each: the sampler's position, the helper's, and the two flags
+    alignas(64) int64_t taken_ = 0;
+    alignas(64) std::atomic<int64_t> count_{0};
+    alignas(64) std::atomic<int> stop_{0};
+    alignas(64) std::atomic<int> busy_{0};
+    alignas(64) char pad_[8] = {0};
+  };
+  // how many helpers this sampler may use (0, 1: the backward direction, 2: both), and whether its model and likelihood allow any: the owner
+  // says so (closed-form gradient, Gram-form likelihood, no gradient check).  Helpers are created at the first transition that can use them.
+  void set_helpers(int n, bool wait = false) { helpersWanted_ = n < 0 ? 0 : (n > 2 ? 2 : n); helpersWait_ = wait; drop_helpers(helpersWanted_); }
+  void set_runahead_allowed(bool ok) { runaheadAllowed_ = ok; if (!ok) drop_helpers(0); }
+  // {leapfrogs taken from a helper, leapfrogs of a helper's direction it had not finished in time (done by this thread itself; in wait mode:
+  // waited for, and counted under "taken" as well), leapfrogs a helper computed that nobody took, transitions without a helper}
+  void runahead_counters(int64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = raCount_[i]; }
+  ~Nuts() { drop_helpers(0); }
 
   Nuts(HostModel& m, const NutsControl& c, unsigned chain, int num_warmup) : model_(m), D_(m.sp.D), skip_(c.skip) {
     rng_.create(c.seed, chain);
@@ -804,6 +1234,53 @@ class Nuts {
   unsigned num_warmup_ = 0, init_buffer_ = 0, term_buffer_ = 0, base_window_ = 0, window_counter_ = 0, next_window_ = 0, window_size_ = 0;
   double wn_ = 0; V wm_, wm2_;
   long nTrans_ = 0, sumDepth_ = 0, sumLeap_ = 0, nDiv_ = 0;
+  // run-ahead: [0] integrates backwards (sign -1), [1] forwards; raDir_ is what the current transition's leaves take their states from
+  std::unique_ptr<RunAhead> ra_[2]; RunAhead* raDir_[2] = {nullptr, nullptr};
+  int helpersWanted_ = 0; bool runaheadAllowed_ = false, vec_ = false, helpersWait_ = false;
+  int64_t raPos_[2] = {0, 0}; bool raGradStale_[2] = {false, false};       // per direction: steps done in this transition; z_.g is older than z_.q
+  int64_t raCount_[4] = {0, 0, 0, 0};
+  void drop_helpers(int keep) {
+    for (int k = 1; k >= keep && k >= 0; --k) if (ra_[k]) { ra_[k].reset(); runahead_budget_give(); }
+  }
+  void ensure_helpers() {
+    // (an array of 2^max_depth states per helper: a model with very many coefficients integrates inline)
+    const size_t cap = (size_t)1 << max_depth_;
+    if (max_depth_ > 20 || cap * ((size_t)3 * D_ + 1) * sizeof(double) > ((size_t)64 << 20)) return;
+    for (int k = 0; k < helpersWanted_; ++k) {
+      if (ra_[k]) continue;
+      if (!runahead_budget_take()) return;
+      try { ra_[k].reset(new RunAhead(model_, D_, cap)); } catch (...) { runahead_budget_give(); return; }   // (no thread to be had: inline)
+      placed_ = false;
+    }
+  }
+  // the helpers follow the sampler's thread from one last-level cache to the next (looked at once per transition; the CPU number comes without
+  // a system call, the topology is read again only when the thread has moved to another CPU)
+  bool placed_ = false, noRoom_ = false;
+#if defined(__linux__)
+  cpu_set_t placedDomain_;
+#endif
+  // false: the thread has no core but its own to put a helper on; this transition runs without
+  bool place_helpers() {
+#if defined(__linux__)
+    const int cpu = sched_getcpu();
+    if (cpu < 0 || cpu >= CPU_SETSIZE) return true;
+    if (placed_ && CPU_ISSET(cpu, &placedDomain_)) return !noRoom_;        // still under the same last-level cache, same helpers
+    cpu_set_t set;
+    const CpuNeighbours::Advice advice = CpuNeighbours::helper_set(cpu, &set, &placedDomain_);
+    placed_ = true; noRoom_ = advice == CpuNeighbours::NOWHERE;
+    if (advice == CpuNeighbours::PLACE) for (int k = 0; k < 2; ++k) if (ra_[k]) ra_[k]->place_on(set);
+    return !noRoom_;
+#else
+    return true;
+#endif
+  }
+  // ends the helpers' work on the transition on every way out of it
+  struct RunAheadScope {
+    Nuts& n;
+    ~RunAheadScope() {
+      for (int k = 0; k < 2; ++k) if (n.raDir_[k]) { n.raCount_[2] += n.raDir_[k]->finish(); n.raDir_[k] = nullptr; }
+    }
+  };
 
   double kinetic() const { double s = 0; for (int i = 0; i < D_; ++i) s += z_.p[(size_t)i] * (inv_metric_[(size_t)i] * z_.p[(size_t)i]); return 0.5 * s; }
   double hamiltonian() const { return kinetic() + z_.Vv; }
@@ -882,22 +1359,30 @@ class Nuts {
     const int D = D_;
     if (depth == 0) {
       const double e = sign * eps_, he = 0.5 * e;
-      {
-        double* __restrict__ const p = z_.p.data(); double* __restrict__ const q = z_.q.data();
-        const double* __restrict__ const g = z_.g.data(); const double* __restrict__ const im = inv_metric_.data();
-        for (int i = 0; i < D; ++i) { const double pi = p[i] - he * g[i]; p[i] = pi; q[i] += e * (im[i] * pi); }
-      }
-      grad();
-      ++acc.n_leapfrog;
-      double kin = 0.0;
-      {
-        double* __restrict__ const p = z_.p.data(); const double* __restrict__ const g = z_.g.data(); const double* __restrict__ const im = inv_metric_.data();
-        double* __restrict__ const sb = sharp_beg.data(); double* __restrict__ const se = sharp_end.data(); double* __restrict__ const rh = rho.data();
-        double* __restrict__ const pb = p_beg.data(); double* __restrict__ const pe = p_end.data();
-        for (int i = 0; i < D; ++i) {
-          const double pi = p[i] - he * g[i], sh = im[i] * pi;
-          p[i] = pi; kin += pi * sh; sb[i] = sh; se[i] = sh; rh[i] += pi; pb[i] = pi; pe[i] = pi;
+      double kin;
+      // A direction with a helper: the helper's state if it is finished.  If the helper is not there yet (it is still waking up, or this
+      // thread is ahead of it) this thread does the step itself, as it would without a helper, and the helper catches up or not: the state
+      // is the same either way.  (helpersWait_: wait for the helper instead, for tests that need every state to come from it.)
+      const int dir = sign < 0 ? 0 : 1;
+      RunAhead* const ra = raDir_[dir];
+      const int64_t k = raPos_[dir]++;
+      bool waited = false;
+      const double* const s = ra ? ra->take(k, helpersWait_, waited) : nullptr;
+      if (s) {
+        std::copy(s, s + D, z_.q.data()); std::copy(s + D, s + 2 * (size_t)D, z_.p.data()); z_.Vv = s[2 * (size_t)D];
+        raGradStale_[dir] = true;      // (z_.g is not brought over: fetched from the helper's array only if this thread does the next step)
+        ++model_.gradEvals; ++raCount_[0]; if (waited) ++raCount_[1];
+        ++acc.n_leapfrog;
+        kin = hostloop::leaf_finish<false>(vec_, D, he, z_.p.data(), z_.g.data(), inv_metric_.data(), sharp_beg.data(), sharp_end.data(), rho.data(), p_beg.data(), p_end.data());
+      } else {
+        if (ra) {
+          ++raCount_[1];
+          if (raGradStale_[dir]) { const double* const g = ra->gradient_of(k - 1); std::copy(g, g + D, z_.g.data()); raGradStale_[dir] = false; }
         }
+        hostloop::kick_drift(vec_, D, e, he, z_.p.data(), z_.q.data(), z_.g.data(), inv_metric_.data());
+        grad();
+        ++acc.n_leapfrog;
+        kin = hostloop::leaf_finish<true>(vec_, D, he, z_.p.data(), z_.g.data(), inv_metric_.data(), sharp_beg.data(), sharp_end.data(), rho.data(), p_beg.data(), p_end.data());
       }
       const double hRaw = 0.5 * kin + z_.Vv, h = finite_or_inf(hRaw);
       if (h - H0 > 1000.0) divergent_ = true;
@@ -919,22 +1404,10 @@ class Nuts {
     else if (rng_.u01() < std::exp(lsw_final - lsw_sub)) std::swap(propose, L.propose_final);
     // rho_sub = rho_init + rho_final; rho += rho_sub; the three criteria (base_nuts.hpp:339-351): the whole subtree, its first half
     // extended by the first momentum of the second, its second half extended by the last momentum of the first
-    double a1 = 0, b1 = 0, a2 = 0, b2 = 0, a3 = 0, b3 = 0;
-    {
-      const double* __restrict__ const ri = L.rho_init.data(); const double* __restrict__ const rf = L.rho_final.data();
-      const double* __restrict__ const pfb = L.p_final_beg.data(); const double* __restrict__ const pie = L.p_init_end.data();
-      const double* __restrict__ const sb = sharp_beg.data(); const double* __restrict__ const se = sharp_end.data();
-      const double* __restrict__ const sfb = L.sharp_final_beg.data(); const double* __restrict__ const sie = L.sharp_init_end.data();
-      double* __restrict__ const rh = rho.data();
-      for (int i = 0; i < D; ++i) {
-        const double rs = ri[i] + rf[i], t2 = ri[i] + pfb[i], t3 = rf[i] + pie[i];
-        rh[i] += rs;
-        a1 += se[i] * rs; b1 += sb[i] * rs;
-        a2 += sfb[i] * t2; b2 += sb[i] * t2;
-        a3 += se[i] * t3; b3 += sie[i] * t3;
-      }
-    }
-    return (a1 > 0 && b1 > 0) & (a2 > 0 && b2 > 0) & (a3 > 0 && b3 > 0);
+    double d[6];
+    hostloop::merge(vec_, D, L.rho_init.data(), L.rho_final.data(), L.p_final_beg.data(), L.p_init_end.data(), sharp_beg.data(), sharp_end.data(),
+                    L.sharp_final_beg.data(), L.sharp_init_end.data(), rho.data(), d);
+    return (d[0] > 0 && d[1] > 0) & (d[2] > 0 && d[3] > 0) & (d[4] > 0 && d[5] > 0);
   }
 
   void nuts_transition() {
@@ -942,8 +1415,18 @@ class Nuts {
     eps_ = nom_eps_;
     if (jitter_) eps_ *= 1.0 + jitter_ * (2.0 * rng_.u01() - 1.0);
     ensure_levels();
+    vec_ = host_vector_on();
     z_.q = cont_;
     draw_momentum(); grad();
+    RunAheadScope scope{*this};
+    raPos_[0] = raPos_[1] = 0; raGradStale_[0] = raGradStale_[1] = false;
+    if (runaheadAllowed_ && helpersWanted_ > 0) {
+      ensure_helpers();
+      const bool room = place_helpers();
+      if (room && ra_[0]) { ra_[0]->start(z_, -eps_, inv_metric_, vec_); raDir_[0] = ra_[0].get(); }
+      if (room && ra_[1]) { ra_[1]->start(z_, eps_, inv_metric_, vec_); raDir_[1] = ra_[1].get(); }
+    }
+    if (!raDir_[0] && !raDir_[1]) ++raCount_[3];
     const double H0 = hamiltonian();
     Pt& fwd = tFwd_; Pt& bck = tBck_; fwd = z_; bck = z_;
     Prop& sample = tSample_; Prop& propose = tPropose_;

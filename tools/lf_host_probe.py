@@ -17,4 +17,6 @@ for rep in range(5):
     t0 = time.perf_counter(); out = s.run(100, False, 2); t1 = time.perf_counter()
     lf = out["stan"][4].sum(); us = 1e6 * (t1 - t0) / lf
     best = us if best is None else min(best, us)
+if hasattr(lib, (sys.argv[2] if len(sys.argv) > 2 else "emu_") + "get_nuts_runahead"):
+    print("run-ahead (S4B_NUTS_HELPERS=%s) over all 650 iterations:" % os.environ.get("S4B_NUTS_HELPERS", "default"), s.get_nuts_runahead())
 print("leapfrogs per iteration %.1f, best of 5: %.3f us per leapfrog (includes the sweeps at n = 2000, T = 5)" % (lf / 100, best))
