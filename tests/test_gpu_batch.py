@@ -1,90 +1,12 @@
 """Sweep groups on the GPU (k_sbatch*, dev_sweep.inc; HipSweepGroup, dev_hip.hip): samplers of one process driven from their own threads,
 their solo sweeps (n <= 4 096) launched together, one workgroup per member.  Every draw must be the one the ungrouped sampler makes."""
-import copy
-import threading
-
 import numpy as np
 import pytest
 
+from batch_cases import _assert_same, _run
 from conftest import assert_chain_parity, friedman_case, run_chain
 
 pytestmark = pytest.mark.gpu
-
-
-def _chain(lib, args, seed, group, out, k):
-    from stan4bart_amd import RRng
-    from stan4bart_amd.abi import Sampler
-    args = copy.copy(args)
-    rng = RRng(seed)
-    args.seed = int(rng.sample_int(2147483647, 1)[0])
-    s = Sampler(lib, "s4b_", args, rng.state)
-    r = {"sweeps0": int(s.get_sweep_stats()[0])}      # (sweeps made at creation, before the sampler joined)
-    try:
-        s.set_trace(True)
-        if group is not None:
-            group.join(s)
-        traces = []
-        if args.warmup > 0:
-            r["warmup"] = s.run(args.warmup, True, 0)
-            traces.append(s.get_trace())
-        s.disengage_adaptation()
-        r["sample"] = s.run(args.iter - args.warmup, False, 0)
-        traces.append(s.get_trace())
-        r["trace"] = np.concatenate(traces)
-        r["trees"] = s.get_trees()
-        if getattr(args, "keep_trees", False):
-            r["kept_trees"] = s.get_kept_trees()
-        r["rng"] = s.get_r_rng_state()
-        r["leaf0"] = s.get_leaf_assignment(0)
-        r["range"] = s.get_bart_data_range()
-        r["pm"] = s.get_parametric_mean()
-        r["sweeps"] = int(s.get_sweep_stats()[0])
-    except Exception as e:      # noqa: BLE001  (surfaced by the caller)
-        r["error"] = e
-    finally:
-        if group is not None:
-            group.leave(s)
-        s.free()
-    out[k] = r
-
-
-def _run(lib, cases, grouped, timeout_s=None):
-    """cases: [(args, seed)], each chain in a thread of its own; grouped: all in one sweep group.  Returns (results, group stats)."""
-    from stan4bart_amd.abi import SweepGroup
-    g = SweepGroup(lib, "s4b_", 0, len(cases)) if grouped else None
-    if g is not None and timeout_s is not None:
-        g.set_timeout(timeout_s)
-    out = {}
-    th = [threading.Thread(target=_chain, args=(lib, a, sd, g, out, k)) for k, (a, sd) in enumerate(cases)]
-    [t.start() for t in th]
-    [t.join(600) for t in th]
-    assert not any(t.is_alive() for t in th), "a chain did not finish"
-    for k in range(len(cases)):
-        assert "error" not in out[k], out[k].get("error")
-    st = None
-    if g is not None:
-        st = g.stats()
-        g.free()
-    return [out[k] for k in range(len(cases))], st
-
-
-def _assert_same(a, b):
-    """bit-identical: the batched launch runs exactly the member's own sweep"""
-    assert np.array_equal(a["trace"], b["trace"])
-    assert np.array_equal(a["rng"], b["rng"])
-    for k in ("tree", "n", "var", "split", "value"):
-        assert np.array_equal(a["trees"][k], b["trees"][k]), k
-    assert np.array_equal(a["leaf0"], b["leaf0"])
-    for ph in ("warmup", "sample"):
-        if ph not in a:
-            continue
-        assert np.array_equal(a[ph]["stan"], b[ph]["stan"]), ph
-        for f in ("train", "test", "varcount"):
-            x, y = a[ph]["bart"].get(f), b[ph]["bart"].get(f)
-            assert (x is None and y is None) or np.array_equal(x, y), (ph, f)
-    if "kept_trees" in a:
-        for k in a["kept_trees"]:
-            assert np.array_equal(a["kept_trees"][k], b["kept_trees"][k]), k
 
 
 def _ihdp(**kw):
