@@ -2,7 +2,8 @@
 //     d(i,k) = v(z_1(i,k)) - v(z_0(i,k)),      v = identity (link 0) or Phi (link 1)
 // summarised on the device: per row mean, sum of squared deviations and type-7 quantiles over the draws, per draw up to PS_GMAX weighted row sums.
 // Included by dev_hip.hip inside namespace s4b, after dev_quantile.inc: the walk, the staging, the tree order of a partial-dependence call, the chunked
-// value scratch and the LDS sort are dev_readout.inc's, dev_pd.inc's and dev_quantile.inc's.
+// value scratch and the LDS sort are dev_readout.inc's, dev_pd.inc's and dev_quantile.inc's.  Shared with the read-outs over one arm or two (dev_groups.inc,
+// readout_projection.inc, readout_spread.inc): contrast_rows, contrast_upload and arm_values_prepare / arm_values_launch.
 //
 // The arms differ in D <= 2 BART columns (found on the host from the BINS of both arms) and in the linear parts whose arm-0 pointer was given.  The
 // host orders the trees of every pooled draw as pd_tree_order does with vars = the D columns: unaffected trees first, affected ones behind them.
@@ -187,25 +188,31 @@ static void contrast_upload(CallBuffers& buf, ContrastDev& a, const ContrastCall
   a.D = c.D; a.var0 = c.D > 0 ? c.vars[0] : -2; a.var1 = c.D > 1 ? c.vars[1] : -2;          // (-2: no node carries it)
 }
 
+// the value kernel of a read-out over one arm or two (contrast, groups, projection, spread): k_contrast_values where `two`, else k_predict_values on the
+// QuantileDev part of `a` — once per call the LDS of the staged route, then a launch per chunk
+static void arm_values_prepare(const ReadoutPlan& plan, bool two) {
+  if (!two) return predict_values_prepare(plan);
+  if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_contrast_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+}
+static void arm_values_launch(hipStream_t stream, const ReadoutPlan& plan, dim3 grid, const ContrastDev& a, bool two) {
+  if (!two) return predict_values_launch(stream, plan, grid, a);
+  if (plan.staged) hipLaunchKernelGGL(k_contrast_values<true>, grid, dim3(PS_BLOCK), plan.lds, stream, a);
+  else hipLaunchKernelGGL(k_contrast_values<false>, grid, dim3(PS_BLOCK), 0, stream, a);
+}
+
 // uploads, up to four launches per chunk of rows, the downloads — on `stream`, everything allocated here freed here (summary_run's discipline)
 static void contrast_run(hipStream_t stream, int P, const ContrastCall& c, int64_t& launches) {
   bool walks;
   SummaryCall r = contrast_rows(c, walks);
   const bool perRow = r.mean != nullptr;
   const ReadoutPlan plan = readout_plan(r, 0, 8, false);          // no reduction space; the workgroups are chosen per chunk
+  const ChunkPlan cp = chunk_plan(r.nT, r.S, c.scratchBytes, QT_SCRATCH_DEFAULT, 1, 64);
   CallBuffers buf(stream);
   const size_t nT = (size_t)r.nT, S = (size_t)r.S, Q = (size_t)c.Q, G = (size_t)r.G;
-  // rows per chunk: quantile_run's rule
-  const int64_t scratch = c.scratchBytes > 0 ? std::min(c.scratchBytes, QT_SCRATCH_DEFAULT) : QT_SCRATCH_DEFAULT;
-  const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(64, scratch / (8 * r.S) / 64 * 64));
-  const int64_t chunks = (r.nT + C - 1) / C;
-  const int64_t slabsMax = (C + CT_SLAB - 1) / CT_SLAB;
-  int Sp = 1; while (Sp < r.S) Sp <<= 1;
-  const int R = std::max(1, QT_SORT / Sp);
-  const size_t sortLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT);
+  const int64_t slabsMax = (cp.C + CT_SLAB - 1) / CT_SLAB;
   ContrastDev a{};
   contrast_upload(buf, a, c, r, P, plan);
-  a.vals = buf.alloc<double>(nullptr, (size_t)C * S);
+  a.vals = buf.alloc<double>(nullptr, (size_t)cp.C * S);
   if (perRow) { a.mean = buf.alloc<double>(nullptr, nT); a.m2 = buf.alloc<double>(nullptr, nT); }
   if (G) {
     a.weights = buf.alloc(r.weights, G * nT);
@@ -214,36 +221,21 @@ static void contrast_run(hipStream_t stream, int P, const ContrastCall& c, int64
   }
   if (Q) { a.probs = buf.alloc(c.probs, Q); a.quantiles = buf.alloc<double>(nullptr, Q * nT); }
   a.G = r.G;
-  a.Q = c.Q; a.Sp = Sp; a.R = R;
-  if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_contrast_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-  if (Q) HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortLds));
-  int64_t mine = 0;
-  for (int64_t ch = 0; ch < chunks; ++ch) {
-    a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0); a.firstChunk = ch == 0;
-    const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
-    // segments of draws: quantile_run's rule
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
-    a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
-    const int segs = (int)((r.S + a.segDraws - 1) / a.segDraws);
-    if (plan.staged) hipLaunchKernelGGL(k_contrast_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, a);
-    else hipLaunchKernelGGL(k_contrast_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, a);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
+  a.Q = c.Q; a.Sp = cp.Sp; a.R = cp.R;
+  arm_values_prepare(plan, true);
+  if (Q) row_quantiles_prepare(cp);
+  LaunchCount launched{launches};
+  for (int64_t ch = 0; ch < cp.chunks; ++ch) {
+    a.chunk0 = ch * cp.C; a.chunkRows = std::min<int64_t>(cp.C, r.nT - a.chunk0); a.firstChunk = ch == 0;
+    arm_values_launch(stream, plan, chunk_grid(a), a, true); launched();
     const int slabs = (int)((a.chunkRows + CT_SLAB - 1) / CT_SLAB);
-    if (perRow || G) {
-      hipLaunchKernelGGL(k_contrast_reduce, dim3(slabs), dim3(CT_BLOCK), 0, stream, a);
-      HIP_OK(hipGetLastError()); ++launches; ++mine;
-    }
+    if (perRow || G) { hipLaunchKernelGGL(k_contrast_reduce, dim3(slabs), dim3(CT_BLOCK), 0, stream, a); launched(); }
     if (G) {
       const int64_t SG = r.S * r.G;
       const int g = (int)std::min<int64_t>(GRID_MAX, (SG + BLOCK - 1) / BLOCK);
-      hipLaunchKernelGGL(k_contrast_fold, dim3(g), dim3(BLOCK), 0, stream, (const double*)a.part, SG, slabs, a.average, a.firstChunk);
-      HIP_OK(hipGetLastError()); ++launches; ++mine;
+      hipLaunchKernelGGL(k_contrast_fold, dim3(g), dim3(BLOCK), 0, stream, (const double*)a.part, SG, slabs, a.average, a.firstChunk); launched();
     }
-    if (Q) {
-      const int sg = (int)((a.chunkRows + R - 1) / R);
-      hipLaunchKernelGGL(k_row_quantiles, dim3(sg), dim3(QT_BLOCK), sortLds, stream, (QuantileDev)a);
-      HIP_OK(hipGetLastError()); ++launches; ++mine;
-    }
+    if (Q) { row_quantiles_launch(stream, cp, a); launched(); }
   }
   if (perRow) {
     HIP_OK(hipMemcpyAsync(r.mean, a.mean, nT * 8, hipMemcpyDeviceToHost, stream));
@@ -252,6 +244,6 @@ static void contrast_run(hipStream_t stream, int P, const ContrastCall& c, int64
   if (G) HIP_OK(hipMemcpyAsync(r.average, a.average, S * G * 8, hipMemcpyDeviceToHost, stream));
   if (Q) HIP_OK(hipMemcpyAsync(c.quantiles, a.quantiles, Q * nT * 8, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
-  r.info[0] = !walks ? 0 : plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = mine;
+  r.info[0] = !walks ? 0 : plan.staged ? 1 : 2; r.info[1] = cp.C; r.info[2] = cp.chunks; r.info[3] = launched.mine;
   r.info[4] = buf.bytes; r.info[5] = r.S; r.info[6] = c.D; r.info[7] = (c.maxAffected << 32) | c.totalAffected;
 }

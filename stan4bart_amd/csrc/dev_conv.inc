@@ -180,23 +180,17 @@ static void conv_run(hipStream_t stream, int P, const ConvCall& c, int64_t& laun
   const int link = r.link;
   if (c.quantity) r.link = 0;                                     // k_predict_values writes z, whatever the response
   const ReadoutPlan plan = readout_plan(r, 0, 4, false);          // no reduction space; the workgroups are chosen per chunk
+  const ChunkPlan cp = chunk_plan(r.nT, r.S, c.scratchBytes, QT_SCRATCH_DEFAULT, 1, 64);
   CallBuffers buf(stream);
   const size_t nT = (size_t)r.nT, S = (size_t)r.S;
-  // rows per chunk, padded draws, rows per workgroup: quantile_run's rules
-  const int64_t scratch = c.scratchBytes > 0 ? std::min(c.scratchBytes, QT_SCRATCH_DEFAULT) : QT_SCRATCH_DEFAULT;
-  const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(64, scratch / (8 * r.S) / 64 * 64));
-  const int64_t chunks = (r.nT + C - 1) / C;
-  int Sp = 1; while (Sp < r.S) Sp <<= 1;
-  const int R = std::max(1, QT_SORT / Sp);
-  const int slots = R >= 4 ? 4 : R;                               // rows in flight: 4 / W
+  const int slots = cp.R >= 4 ? 4 : cp.R;                         // rows in flight: 4 / W
   if (c.numChains < 1 || c.numChains > CV_CHAINS_MAX || c.chainLen < 1) throw std::logic_error("conv_run: chains out of range");
   for (int x = 0; x < c.numChains; ++x)
     if (c.chainStart[x] < 0 || (int64_t)c.chainStart[x] + c.chainLen > r.S) throw std::logic_error("conv_run: a chain leaves the pooled row");
-  const size_t rowLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT) + (size_t)8 * CV_RED + (size_t)16 * (size_t)slots * (size_t)c.numChains
-                        + (size_t)8 * (size_t)slots * 4 * CV_LAGS;
+  const size_t rowLds = cp.sortLds + (size_t)8 * CV_RED + (size_t)16 * (size_t)slots * (size_t)c.numChains + (size_t)8 * (size_t)slots * 4 * CV_LAGS;
   ConvDev a{};
   buf.upload_rows(a, r, P, plan.stageNodes);
-  a.vals = buf.alloc<double>(nullptr, (size_t)C * S);
+  a.vals = buf.alloc<double>(nullptr, (size_t)cp.C * S);
   if (c.quantity) {
     if (!link) { a.sigma = buf.alloc(c.sigma, S); if (c.rowScale) a.rowScale = buf.alloc(c.rowScale, nT); }
     a.y = buf.alloc(c.y, nT);
@@ -208,22 +202,14 @@ static void conv_run(hipStream_t stream, int P, const ConvCall& c, int64_t& laun
   if (c.mcse) a.mcse = buf.alloc<double>(nullptr, nT);
   if (c.nPairs) a.nPairs = buf.alloc<int32_t>(nullptr, nT);
   a.quantity = c.quantity; a.convLink = link; a.C = c.numChains; a.N = c.chainLen;
-  a.Q = 0; a.Sp = Sp; a.R = R;
-  if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_predict_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+  a.Q = 0; a.Sp = cp.Sp; a.R = cp.R;
+  predict_values_prepare(plan);
   HIP_OK(hipFuncSetAttribute((const void*)k_chain_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
-  for (int64_t ch = 0; ch < chunks; ++ch) {
-    a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0);
-    const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
-    // segments of draws: quantile_run's rule
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
-    a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
-    const int segs = (int)((r.S + a.segDraws - 1) / a.segDraws);
-    if (plan.staged) hipLaunchKernelGGL(k_predict_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, (QuantileDev)a);
-    else hipLaunchKernelGGL(k_predict_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, (QuantileDev)a);
-    HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
-    const int sg = (int)((a.chunkRows + R - 1) / R);
-    hipLaunchKernelGGL(k_chain_rows, dim3(sg), dim3(QT_BLOCK), rowLds, stream, a);
-    HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
+  LaunchCount launched{launches};
+  for (int64_t ch = 0; ch < cp.chunks; ++ch) {
+    a.chunk0 = ch * cp.C; a.chunkRows = std::min<int64_t>(cp.C, r.nT - a.chunk0);
+    predict_values_launch(stream, plan, chunk_grid(a), a); launched();
+    hipLaunchKernelGGL(k_chain_rows, dim3((unsigned)((a.chunkRows + cp.R - 1) / cp.R)), dim3(QT_BLOCK), rowLds, stream, a); launched();
   }
   if (a.rhat) HIP_OK(hipMemcpyAsync(c.rhat, a.rhat, nT * 8, hipMemcpyDeviceToHost, stream));
   if (a.ess) HIP_OK(hipMemcpyAsync(c.ess, a.ess, nT * 8, hipMemcpyDeviceToHost, stream));
@@ -231,6 +217,6 @@ static void conv_run(hipStream_t stream, int P, const ConvCall& c, int64_t& laun
   if (a.mcse) HIP_OK(hipMemcpyAsync(c.mcse, a.mcse, nT * 8, hipMemcpyDeviceToHost, stream));
   if (a.nPairs) HIP_OK(hipMemcpyAsync(c.nPairs, a.nPairs, nT * 4, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
-  r.info[0] = plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = ((int64_t)R << 32) | (int64_t)Sp;
-  r.info[4] = r.maxDrawNodes; r.info[6] = buf.bytes; r.info[7] = r.S;
+  r.info[0] = plan.staged ? 1 : 2; r.info[1] = cp.C; r.info[2] = cp.chunks; r.info[3] = ((int64_t)cp.R << 32) | (int64_t)cp.Sp;
+  r.info[4] = r.maxDrawNodes; r.info[5] = launched.mine; r.info[6] = buf.bytes; r.info[7] = r.S;
 }

@@ -4,12 +4,13 @@
 //     A(l,k) = a(l,k) (statistic 0) or a(l,k) / W_l (statistic 1),
 // and per level the mean, m2 and type-7 quantiles of A(l, .) and the share of the draws above a threshold.
 // Included by dev_hip.hip inside namespace s4b, LAST, after dev_contrast.inc: the value kernels, the chunked scratch, the LDS sort and the call
-// scaffold are dev_readout.inc's, dev_quantile.inc's and dev_contrast.inc's.  New here is the segmented reduction over the rows by level.
+// scaffold are dev_readout.inc's, dev_quantile.inc's and dev_contrast.inc's.  New here is the segmented reduction over the rows by level.  Shared with
+// the read-outs behind it (projection, spread, check, curves): k_level_rows and LevelsSummary, the summary over the draws of a matrix of unit-weight levels.
 //
 // THE ORDER OF THE ADDITIONS (include/stan4bart_amd.h states it, tests/group_cases.py models it): slabs are the GLOBAL blocks of GP_SLAB rows — a chunk
 // starts on a multiple of GP_SLAB, so a slab never depends on the chunking.  a(l,k) is the left fold, over the slabs in ascending order, of the slab's
 // partial; a partial is the left fold, over the level's rows of the slab in row order, of w_i x(i,k); the first term of a fold is taken as it is.
-// Per chunk of C rows (C as quantile_run chooses it):
+// Per chunk of C rows (chunk_plan):
 //   k_predict_values<STAGED> / k_contrast_values<STAGED>   unchanged: the chunk's values row-major in the scratch.
 //   k_level_reduce    one workgroup (a wave) per slab and segment of GP_BLOCK draws, a draw per thread: vals[r S + k] is read coalesced across the wave,
 //                     level[r] and w[r] are the same for every lane (scalar loads).  A thread runs down the slab's rows and closes a partial whenever
@@ -105,6 +106,47 @@ __global__ __launch_bounds__(BLOCK) void k_level_rows(GroupsDev a) {
   }
 }
 
+// The summary over the draws of a device matrix [n x S] whose rows are levels (groups: its level matrix; projection, spread, check, curves: a matrix
+// of statistics or values whose every row is a level of ONE row and unit weight, statistic 0): per row the mean and m2 through k_level_rows and the
+// type-7 quantiles through k_row_quantiles, in pieces of at most GP_SORT_LEVELS rows, written at a row offset of the outputs.
+struct LevelsSummary {
+  std::vector<int64_t> start; std::vector<double> ones;          // the host side of the unit tables: the uploads read it until the call has synchronised
+  GroupsDev g{};                                                 // the unit tables of a piece (levelStart 0, 1, 2, ...; levelWeight 1), S, statistic 0, no threshold
+  QuantileDev qd{};                                              // the probs, S, Q, Sp, R
+  ChunkPlan cp{};
+  // once per call: the probs (Q > 0) uploaded and the sort prepared; unitRows > 0: the unit tables for pieces of at most that many rows uploaded
+  void prepare(CallBuffers& buf, const ChunkPlan& plan, int64_t S, const double* probs, int Q, int64_t unitRows) {
+    cp = plan;
+    g.S = S;
+    if (unitRows > 0) {
+      const size_t piece = (size_t)std::min<int64_t>(GP_SORT_LEVELS, unitRows);
+      start.resize(piece + 1);
+      for (size_t l = 0; l <= piece; ++l) start[l] = (int64_t)l;
+      ones.assign(piece, 1.0);
+      g.levelStart = buf.alloc(start.data(), piece + 1); g.levelWeight = buf.alloc(ones.data(), piece);
+    }
+    if (Q) {
+      qd.probs = buf.alloc(probs, (size_t)Q); qd.S = S; qd.Q = Q; qd.Sp = plan.Sp; qd.R = plan.R;
+      row_quantiles_prepare(plan);
+    }
+  }
+  // the n rows of vals [n x S] into rows [first, first + n) of the device outputs mean, m2 [total] and quantiles [Q x total], each where not NULL
+  void run(hipStream_t stream, LaunchCount& launched, double* vals, int64_t n, int64_t first, double* mean, double* m2, double* quantiles, int64_t total) {
+    qd.quantiles = quantiles; qd.nT = total;
+    for (int64_t l0 = 0; l0 < n; l0 += GP_SORT_LEVELS) {
+      const int64_t L = std::min<int64_t>(GP_SORT_LEVELS, n - l0);
+      if (mean || m2) {
+        g.lev = vals + (size_t)l0 * (size_t)g.S; g.L = L; g.mean = mean ? mean + first + l0 : nullptr; g.m2 = m2 ? m2 + first + l0 : nullptr;
+        hipLaunchKernelGGL(k_level_rows, dim3((unsigned)std::min<int64_t>(GRID_MAX, (L + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, stream, g); launched();
+      }
+      if (quantiles) {
+        qd.vals = vals + (size_t)l0 * (size_t)g.S; qd.chunk0 = first + l0; qd.chunkRows = L;
+        row_quantiles_launch(stream, cp, qd); launched();
+      }
+    }
+  }
+};
+
 // uploads, per chunk the value kernel, the reduce and the fold, then the level kernels and the downloads — on `stream`, everything allocated here
 // freed here (summary_run's discipline)
 static void groups_run(hipStream_t stream, int P, const GroupsCall& c, int64_t& launches) {
@@ -113,23 +155,17 @@ static void groups_run(hipStream_t stream, int P, const GroupsCall& c, int64_t& 
   bool walks = true;
   SummaryCall r = two ? contrast_rows(ar, walks) : ar.rows;
   const ReadoutPlan plan = readout_plan(r, 0, two ? 8 : 4, false);
+  const ChunkPlan cp = chunk_plan(r.nT, r.S, ar.scratchBytes, QT_SCRATCH_DEFAULT, 1, 64);
   CallBuffers buf(stream);
   const size_t nT = (size_t)r.nT, S = (size_t)r.S, Q = (size_t)ar.Q, L = (size_t)c.L;
-  // rows per chunk: quantile_run's rule
-  const int64_t scratch = ar.scratchBytes > 0 ? std::min(ar.scratchBytes, QT_SCRATCH_DEFAULT) : QT_SCRATCH_DEFAULT;
-  const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(64, scratch / (8 * r.S) / 64 * 64));
-  const int64_t chunks = (r.nT + C - 1) / C;
-  const int64_t slabsMax = (C + GP_SLAB - 1) / GP_SLAB;
-  int Sp = 1; while (Sp < r.S) Sp <<= 1;
-  const int R = std::max(1, QT_SORT / Sp);
-  const size_t sortLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT);
+  const int64_t slabsMax = (cp.C + GP_SLAB - 1) / GP_SLAB;
   // the levels that touch more than one slab, ascending
   std::vector<int32_t> edgeLevel;
   for (int64_t l = 0; l < c.L; ++l)
     if (c.levelStart[l + 1] > c.levelStart[l] && c.levelStart[l] / GP_SLAB != (c.levelStart[l + 1] - 1) / GP_SLAB) edgeLevel.push_back((int32_t)l);
   ContrastDev a{};
   if (two) contrast_upload(buf, a, ar, r, P, plan); else buf.upload_rows(a, r, P, plan.stageNodes);
-  a.vals = buf.alloc<double>(nullptr, (size_t)C * S);
+  a.vals = buf.alloc<double>(nullptr, (size_t)cp.C * S);
   GroupsDev g{};
   g.vals = a.vals;
   g.level = buf.alloc(c.level, nT);
@@ -143,58 +179,35 @@ static void groups_run(hipStream_t stream, int P, const GroupsCall& c, int64_t& 
   if (c.m2) g.m2 = buf.alloc<double>(nullptr, L);
   if (c.pAbove) g.pAbove = buf.alloc<double>(nullptr, L);
   g.nT = r.nT; g.S = r.S; g.L = c.L; g.statistic = c.statistic; g.hasThreshold = c.hasThreshold; g.threshold = c.threshold;
-  QuantileDev qd{};
-  if (Q) { qd.probs = buf.alloc(ar.probs, Q); qd.quantiles = buf.alloc<double>(nullptr, Q * L); qd.nT = c.L; qd.S = r.S; qd.Q = ar.Q; qd.Sp = Sp; qd.R = R; }
-  if (plan.staged) {
-    if (two) HIP_OK(hipFuncSetAttribute((const void*)k_contrast_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-    else HIP_OK(hipFuncSetAttribute((const void*)k_predict_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-  }
-  if (Q) HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortLds));
-  int64_t mine = 0;
+  LevelsSummary sum;          // its sort alone: the levels here have tables, a statistic and a threshold of their own
+  sum.prepare(buf, cp, r.S, ar.probs, ar.Q, 0);
+  double* quantiles = Q ? buf.alloc<double>(nullptr, Q * L) : nullptr;
+  arm_values_prepare(plan, two);
+  LaunchCount launched{launches};
   size_t e0 = 0, e1 = 0;          // edgeLevel[e0 .. e1): the levels with rows in the chunk
-  for (int64_t ch = 0; ch < chunks; ++ch) {
-    a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0);
+  for (int64_t ch = 0; ch < cp.chunks; ++ch) {
+    a.chunk0 = ch * cp.C; a.chunkRows = std::min<int64_t>(cp.C, r.nT - a.chunk0);
     g.chunk0 = a.chunk0; g.chunkRows = a.chunkRows;
-    const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
-    // segments of draws: quantile_run's rule
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
-    a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
-    const int segs = (int)((r.S + a.segDraws - 1) / a.segDraws);
-    if (two) {
-      if (plan.staged) hipLaunchKernelGGL(k_contrast_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, a);
-      else hipLaunchKernelGGL(k_contrast_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, a);
-    } else {
-      if (plan.staged) hipLaunchKernelGGL(k_predict_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, (QuantileDev)a);
-      else hipLaunchKernelGGL(k_predict_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, (QuantileDev)a);
-    }
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
+    arm_values_launch(stream, plan, chunk_grid(a), a, two); launched();
     const int slabs = (int)((a.chunkRows + GP_SLAB - 1) / GP_SLAB);
-    hipLaunchKernelGGL(k_level_reduce, dim3(slabs, (unsigned)((r.S + GP_BLOCK - 1) / GP_BLOCK)), dim3(GP_BLOCK), 0, stream, g);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
+    hipLaunchKernelGGL(k_level_reduce, dim3(slabs, (unsigned)((r.S + GP_BLOCK - 1) / GP_BLOCK)), dim3(GP_BLOCK), 0, stream, g); launched();
     const int64_t end = a.chunk0 + a.chunkRows;
     while (e0 < edgeLevel.size() && c.levelStart[edgeLevel[e0] + 1] <= a.chunk0) ++e0;
     e1 = std::max(e1, e0);
     while (e1 < edgeLevel.size() && c.levelStart[edgeLevel[e1]] < end) ++e1;
     if (e1 > e0) {
       const int64_t n = (int64_t)(e1 - e0) * r.S;
-      hipLaunchKernelGGL(k_level_fold, dim3((unsigned)std::min<int64_t>(GRID_MAX, (n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, g, (int64_t)e0, (int64_t)(e1 - e0));
-      HIP_OK(hipGetLastError()); ++launches; ++mine;
+      hipLaunchKernelGGL(k_level_fold, dim3((unsigned)std::min<int64_t>(GRID_MAX, (n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, g, (int64_t)e0, (int64_t)(e1 - e0)); launched();
     }
   }
-  hipLaunchKernelGGL(k_level_rows, dim3((unsigned)std::min<int64_t>(GRID_MAX, (c.L + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, stream, g);
-  HIP_OK(hipGetLastError()); ++launches; ++mine;
-  if (Q)
-    for (int64_t l0 = 0; l0 < c.L; l0 += GP_SORT_LEVELS) {
-      qd.vals = g.lev + (size_t)l0 * S; qd.chunk0 = l0; qd.chunkRows = std::min<int64_t>(GP_SORT_LEVELS, c.L - l0);
-      hipLaunchKernelGGL(k_row_quantiles, dim3((unsigned)((qd.chunkRows + R - 1) / R)), dim3(QT_BLOCK), sortLds, stream, qd);
-      HIP_OK(hipGetLastError()); ++launches; ++mine;
-    }
+  hipLaunchKernelGGL(k_level_rows, dim3((unsigned)std::min<int64_t>(GRID_MAX, (c.L + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, stream, g); launched();
+  if (Q) sum.run(stream, launched, g.lev, c.L, 0, nullptr, nullptr, quantiles, c.L);
   if (c.mean) HIP_OK(hipMemcpyAsync(c.mean, g.mean, L * 8, hipMemcpyDeviceToHost, stream));
   if (c.m2) HIP_OK(hipMemcpyAsync(c.m2, g.m2, L * 8, hipMemcpyDeviceToHost, stream));
   if (c.pAbove) HIP_OK(hipMemcpyAsync(c.pAbove, g.pAbove, L * 8, hipMemcpyDeviceToHost, stream));
-  if (Q) HIP_OK(hipMemcpyAsync(c.quantiles, qd.quantiles, Q * L * 8, hipMemcpyDeviceToHost, stream));
+  if (Q) HIP_OK(hipMemcpyAsync(c.quantiles, quantiles, Q * L * 8, hipMemcpyDeviceToHost, stream));
   if (c.draws) HIP_OK(hipMemcpyAsync(c.draws, g.lev, L * S * 8, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
-  r.info[0] = !walks ? 0 : plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = mine;
+  r.info[0] = !walks ? 0 : plan.staged ? 1 : 2; r.info[1] = cp.C; r.info[2] = cp.chunks; r.info[3] = launched.mine;
   r.info[4] = buf.bytes; r.info[5] = r.S; r.info[6] = (int64_t)edgeLevel.size(); r.info[7] = c.nanLevels;
 }

@@ -157,20 +157,15 @@ static void loo_run(hipStream_t stream, int P, const LooCall& c, int64_t& launch
   const int link = r.link;
   r.link = 0;                                                     // k_predict_values writes z, whatever the response
   const ReadoutPlan plan = readout_plan(r, 0, 4, false);          // no reduction space; the workgroups are chosen per chunk
+  const ChunkPlan cp = chunk_plan(r.nT, r.S, c.scratchBytes, QT_SCRATCH_DEFAULT, 1, 64);
   CallBuffers buf(stream);
   const size_t nT = (size_t)r.nT, S = (size_t)r.S;
-  // rows per chunk, padded draws, rows per sort workgroup: quantile_run's rules
-  const int64_t scratch = c.scratchBytes > 0 ? std::min(c.scratchBytes, QT_SCRATCH_DEFAULT) : QT_SCRATCH_DEFAULT;
-  const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(64, scratch / (8 * r.S) / 64 * 64));
-  const int64_t chunks = (r.nT + C - 1) / C;
-  int Sp = 1; while (Sp < r.S) Sp <<= 1;
-  const int R = std::max(1, QT_SORT / Sp);
-  const int slots = R >= 4 ? 4 : R;                               // rows in flight: 4 / W
+  const int slots = cp.R >= 4 ? 4 : cp.R;                         // rows in flight: 4 / W
   if (c.tailLen < 0 || c.tailLen > LOO_TAIL_MAX || (c.tailLen >= 5 && c.tailLen > r.S - 1)) throw std::logic_error("loo_run: tail length out of range");
-  const size_t rowLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT) + (size_t)8 * LOO_RED + (size_t)8 * (size_t)slots * (size_t)c.tailLen;
+  const size_t rowLds = cp.sortLds + (size_t)8 * LOO_RED + (size_t)8 * (size_t)slots * (size_t)c.tailLen;
   LooDev a{};
   buf.upload_rows(a, r, P, plan.stageNodes);
-  a.vals = buf.alloc<double>(nullptr, (size_t)C * S);
+  a.vals = buf.alloc<double>(nullptr, (size_t)cp.C * S);
   if (!link) { a.sigma = buf.alloc(c.sigma, S); if (c.rowScale) a.rowScale = buf.alloc(c.rowScale, nT); }
   a.y = buf.alloc(c.y, nT);
   if (c.elpd) a.elpd = buf.alloc<double>(nullptr, nT);
@@ -180,28 +175,20 @@ static void loo_run(hipStream_t stream, int P, const LooCall& c, int64_t& launch
   a.looLink = link; a.M = c.tailLen;
   int rt = 0; while ((rt + 1) * (rt + 1) <= a.M) ++rt;            // floor(sqrt M), in integers
   a.G = 30 + rt; a.quart = std::max(0, (2 * a.M + 4) / 8 - 1);    // floor(M / 4 + 0.5) - 1 = floor((2 M + 4) / 8) - 1
-  a.Q = 0; a.Sp = Sp; a.R = R;
-  if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_predict_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+  a.Q = 0; a.Sp = cp.Sp; a.R = cp.R;
+  predict_values_prepare(plan);
   HIP_OK(hipFuncSetAttribute((const void*)k_loo_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
-  for (int64_t ch = 0; ch < chunks; ++ch) {
-    a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0);
-    const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
-    // segments of draws: quantile_run's rule
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
-    a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
-    const int segs = (int)((r.S + a.segDraws - 1) / a.segDraws);
-    if (plan.staged) hipLaunchKernelGGL(k_predict_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, (QuantileDev)a);
-    else hipLaunchKernelGGL(k_predict_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, (QuantileDev)a);
-    HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
-    const int sg = (int)((a.chunkRows + R - 1) / R);
-    hipLaunchKernelGGL(k_loo_rows, dim3(sg), dim3(QT_BLOCK), rowLds, stream, a);
-    HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
+  LaunchCount launched{launches};
+  for (int64_t ch = 0; ch < cp.chunks; ++ch) {
+    a.chunk0 = ch * cp.C; a.chunkRows = std::min<int64_t>(cp.C, r.nT - a.chunk0);
+    predict_values_launch(stream, plan, chunk_grid(a), a); launched();
+    hipLaunchKernelGGL(k_loo_rows, dim3((unsigned)((a.chunkRows + cp.R - 1) / cp.R)), dim3(QT_BLOCK), rowLds, stream, a); launched();
   }
   if (a.elpd) HIP_OK(hipMemcpyAsync(c.elpd, a.elpd, nT * 8, hipMemcpyDeviceToHost, stream));
   if (a.khat) HIP_OK(hipMemcpyAsync(c.khat, a.khat, nT * 8, hipMemcpyDeviceToHost, stream));
   if (a.lpd) HIP_OK(hipMemcpyAsync(c.lpd, a.lpd, nT * 8, hipMemcpyDeviceToHost, stream));
   if (a.ess) HIP_OK(hipMemcpyAsync(c.ess, a.ess, nT * 8, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
-  r.info[0] = plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = ((int64_t)R << 32) | (int64_t)Sp;
-  r.info[4] = r.maxDrawNodes; r.info[6] = buf.bytes; r.info[7] = r.S;
+  r.info[0] = plan.staged ? 1 : 2; r.info[1] = cp.C; r.info[2] = cp.chunks; r.info[3] = ((int64_t)cp.R << 32) | (int64_t)cp.Sp;
+  r.info[4] = r.maxDrawNodes; r.info[5] = launched.mine; r.info[6] = buf.bytes; r.info[7] = r.S;
 }

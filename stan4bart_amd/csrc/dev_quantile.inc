@@ -1,5 +1,7 @@
 // Per-row quantiles of the kept draws' predictions, pooled over several samplers (s4b_predict_quantiles; DESIGN.md 5.7).
 // Included by dev_hip.hip inside namespace s4b, after dev_summary.inc and, through it, dev_readout.inc: the walk, the staging, the linear part, the out-of-line Phi and the route are there.
+// Shared with every chunked read-out behind it (the host side, below the kernels): LaunchCount, ChunkPlan / chunk_plan (rows per chunk, padded draws, rows per
+// sort workgroup), chunk_grid (segments of draws), predict_values_prepare / _launch and row_quantiles_prepare / _launch.
 //
 // The host hands down ONE pooled description (QuantileCall.rows: the kept draws of the sampler and its peers concatenated, S draws) and loops over
 // chunks of C rows.  Per chunk two launches on the sampler's stream:
@@ -133,43 +135,76 @@ __global__ __launch_bounds__(QT_BLOCK) void k_row_quantiles(QuantileDev a) {
   qt_type7_rows(a, key, row0);
 }
 
+// ---- the host side that every chunked read-out shares (DESIGN.md 5.7): the launch count, the chunk plan, a chunk's launch grid, the launches of
+// k_predict_values and of k_row_quantiles.  A *_run keeps its own plain loop over the chunks and calls these inside it.
+
+// the launch just made: checked, and counted for the sampler and for the call
+struct LaunchCount {
+  int64_t& launches; int64_t mine = 0;
+  void operator()() { HIP_OK(hipGetLastError()); ++launches; ++mine; }
+};
+
+// how a call cuts its rows into chunks and sorts a row of draws: C rows per chunk, Sp = S rounded up to a power of two, R rows per sort workgroup
+struct ChunkPlan { int64_t C, chunks; int Sp, R; size_t sortLds; };
+// rows per chunk: what the scratch holds (the call's scratch_bytes, at most and by default scratchDefault; perRowDraw values of 8 bytes per row and
+// draw), a multiple of `multiple`, at least that, at most all rows
+static ChunkPlan chunk_plan(int64_t nT, int64_t S, int64_t scratchBytes, int64_t scratchDefault, int64_t perRowDraw, int64_t multiple) {
+  ChunkPlan p;
+  const int64_t scratch = scratchBytes > 0 ? std::min(scratchBytes, scratchDefault) : scratchDefault;
+  p.C = std::min<int64_t>(nT, std::max<int64_t>(multiple, scratch / (8 * S * perRowDraw) / multiple * multiple));
+  p.chunks = (nT + p.C - 1) / p.C;
+  p.Sp = 1; while (p.Sp < S) p.Sp <<= 1;
+  p.R = std::max(1, QT_SORT / p.Sp);
+  p.sortLds = (size_t)8 * (size_t)std::max(p.Sp, QT_SORT);
+  return p;
+}
+// the grid of a value kernel over the chunk a.chunkRows: tiles of PS_BLOCK rows times segments of a.segDraws draws, which is set here
+static dim3 chunk_grid(QuantileDev& a) {
+  const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
+  // segments of draws: enough to reach QT_FILL workgroups, each of at least QT_SEG_MIN draws and a multiple of QT_GROUP (a thread's store groups stay whole)
+  const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, a.S / QT_SEG_MIN));
+  a.segDraws = ((a.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
+  return dim3(wg, (unsigned)((a.S + a.segDraws - 1) / a.segDraws));
+}
+// k_predict_values: once per call the LDS of the staged route, then a launch per chunk (a read-out's own *Dev goes in as its QuantileDev part)
+static void predict_values_prepare(const ReadoutPlan& plan) {
+  if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_predict_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+}
+static void predict_values_launch(hipStream_t stream, const ReadoutPlan& plan, dim3 grid, const QuantileDev& a) {
+  if (plan.staged) hipLaunchKernelGGL(k_predict_values<true>, grid, dim3(PS_BLOCK), plan.lds, stream, a);
+  else hipLaunchKernelGGL(k_predict_values<false>, grid, dim3(PS_BLOCK), 0, stream, a);
+}
+// k_row_quantiles: once per call its LDS, then a launch over the a.chunkRows rows at a.vals
+static void row_quantiles_prepare(const ChunkPlan& cp) {
+  HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cp.sortLds));
+}
+static void row_quantiles_launch(hipStream_t stream, const ChunkPlan& cp, const QuantileDev& a) {
+  hipLaunchKernelGGL(k_row_quantiles, dim3((unsigned)((a.chunkRows + cp.R - 1) / cp.R)), dim3(QT_BLOCK), cp.sortLds, stream, a);
+}
+
 // uploads, two launches per chunk of rows, the download — on `stream`, everything allocated here freed here (summary_run's discipline)
 static void quantile_run(hipStream_t stream, int P, const QuantileCall& c, int64_t& launches) {
   const SummaryCall& r = c.rows;
   const ReadoutPlan plan = readout_plan(r, 0, 4, false);          // no reduction space; the workgroups are chosen per chunk
+  const ChunkPlan cp = chunk_plan(r.nT, r.S, c.scratchBytes, QT_SCRATCH_DEFAULT, 1, 64);
   CallBuffers buf(stream);
   const size_t nT = (size_t)r.nT, S = (size_t)r.S, Q = (size_t)c.Q;
-  // rows per chunk: what the scratch holds, a multiple of 64, at least 64, at most all rows
-  const int64_t scratch = c.scratchBytes > 0 ? std::min(c.scratchBytes, QT_SCRATCH_DEFAULT) : QT_SCRATCH_DEFAULT;
-  const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(64, scratch / (8 * r.S) / 64 * 64));
-  const int64_t chunks = (r.nT + C - 1) / C;
-  int Sp = 1; while (Sp < r.S) Sp <<= 1;
-  const int R = std::max(1, QT_SORT / Sp);
-  const size_t sortLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT);
   QuantileDev a{};
   buf.upload_rows(a, r, P, plan.stageNodes);
-  a.vals = buf.alloc<double>(nullptr, (size_t)C * S);
+  a.vals = buf.alloc<double>(nullptr, (size_t)cp.C * S);
   a.probs = buf.alloc(c.probs, Q);
   a.quantiles = buf.alloc<double>(nullptr, Q * nT);
-  a.Q = c.Q; a.Sp = Sp; a.R = R;
-  if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_predict_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-  HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortLds));
-  for (int64_t ch = 0; ch < chunks; ++ch) {
-    a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0);
-    const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
-    // segments of draws: enough to reach QT_FILL workgroups, each of at least QT_SEG_MIN draws and a multiple of QT_GROUP (a thread's store groups stay whole)
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
-    a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
-    const int segs = (int)((r.S + a.segDraws - 1) / a.segDraws);
-    if (plan.staged) hipLaunchKernelGGL(k_predict_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, a);
-    else hipLaunchKernelGGL(k_predict_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, a);
-    HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
-    const int sg = (int)((a.chunkRows + R - 1) / R);
-    hipLaunchKernelGGL(k_row_quantiles, dim3(sg), dim3(QT_BLOCK), sortLds, stream, a);
-    HIP_OK(hipGetLastError()); ++launches; ++r.info[5];
+  a.Q = c.Q; a.Sp = cp.Sp; a.R = cp.R;
+  predict_values_prepare(plan);
+  row_quantiles_prepare(cp);
+  LaunchCount launched{launches};
+  for (int64_t ch = 0; ch < cp.chunks; ++ch) {
+    a.chunk0 = ch * cp.C; a.chunkRows = std::min<int64_t>(cp.C, r.nT - a.chunk0);
+    predict_values_launch(stream, plan, chunk_grid(a), a); launched();
+    row_quantiles_launch(stream, cp, a); launched();
   }
   HIP_OK(hipMemcpyAsync(c.quantiles, a.quantiles, Q * nT * 8, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
-  r.info[0] = plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = ((int64_t)R << 32) | (int64_t)Sp;
-  r.info[4] = r.maxDrawNodes; r.info[6] = buf.bytes; r.info[7] = r.S;
+  r.info[0] = plan.staged ? 1 : 2; r.info[1] = cp.C; r.info[2] = cp.chunks; r.info[3] = ((int64_t)cp.R << 32) | (int64_t)cp.Sp;
+  r.info[4] = r.maxDrawNodes; r.info[5] = launched.mine; r.info[6] = buf.bytes; r.info[7] = r.S;
 }

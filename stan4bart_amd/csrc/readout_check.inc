@@ -29,7 +29,7 @@
 //   from +0, a row with w_i = 0 adding no term (under link 1 its log Phi may be -inf: 0 x -inf is not formed); over the slabs added in ascending
 //   order; D holds total / W (link 0) and (-2 total) / W (link 1).
 //   Extremes are order-free.
-// Per chunk of C rows (C as spread_run chooses it, in whole slabs):
+// Per chunk of C rows (chunk_plan, in whole slabs of SP_SLAB rows):
 //   k_predict_values<STAGED>   unchanged, link 0: the chunk's z row-major in the scratch.
 //   k_check_reduce<LINK, BINS, SEARCH> k_spread_reduce's shape: one wave per slab and block of SP_BLOCK draws, a draw per lane; the loads of CK_AHEAD rows of
 //                       z are issued together; w, y and row_scale of a row are wave-uniform loads; sigma[k] is loaded once per lane.  Per row the
@@ -261,22 +261,13 @@ static void check_run(hipStream_t stream, int P, const CheckCall& c, int64_t& la
   const int link = r.link;
   r.link = 0;                                                     // k_predict_values writes z, whatever the response
   const ReadoutPlan plan = readout_plan(r, 0, 4, false);
+  const ChunkPlan cp = chunk_plan(r.nT, r.S, c.scratchBytes, QT_SCRATCH_DEFAULT, 1, SP_SLAB);          // whole slabs
   CallBuffers buf(stream);
   const size_t nT = (size_t)r.nT, S = (size_t)r.S, Q = (size_t)c.Q, T = (size_t)c.T, L = CK_STATS + T, R = CK_MOMENTS + (T ? T + 1 : 0);
-  // rows per chunk: spread_run's rule, in whole slabs of SP_SLAB rows
-  const int64_t scratch = c.scratchBytes > 0 ? std::min(c.scratchBytes, QT_SCRATCH_DEFAULT) : QT_SCRATCH_DEFAULT;
-  const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(SP_SLAB, scratch / (8 * r.S) / SP_SLAB * SP_SLAB));
-  const int64_t chunks = (r.nT + C - 1) / C;
-  const int64_t slabsMax = (C + SP_SLAB - 1) / SP_SLAB;
-  int Sp = 1; while (Sp < r.S) Sp <<= 1;
-  const int Rq = std::max(1, QT_SORT / Sp);
-  const size_t sortLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT);
+  const int64_t C = cp.C, slabsMax = (C + SP_SLAB - 1) / SP_SLAB;
   const bool search = c.T > 0 && (c.binIndex == 2 || (c.binIndex == 0 && c.T >= SP_SEARCH_MIN));
   const size_t binLds = T ? ((T + 1) * SP_BLOCK + (search ? T : 0)) * 8 : 0;
   if (c.observed) check_observed(c.y, c.rowWeights, r.nT, c.T, c.thresholds, c.W, c.observed);
-  std::vector<int64_t> start(L + 1);
-  for (size_t l = 0; l <= L; ++l) start[l] = (int64_t)l;
-  const std::vector<double> ones(L, 1.0);
   QuantileDev a{};
   buf.upload_rows(a, r, P, plan.stageNodes);
   a.vals = buf.alloc<double>(nullptr, (size_t)C * S);
@@ -295,57 +286,37 @@ static void check_run(hipStream_t stream, int P, const CheckCall& c, int64_t& la
   p.out = buf.alloc<double>(nullptr, L * S);
   p.S = r.S; p.T = c.T; p.link = link; p.W = c.W;
   p.key0 = (uint32_t)c.noiseKey; p.key1 = (uint32_t)(c.noiseKey >> 32);
-  GroupsDev g{};
-  g.lev = p.out; g.levelStart = buf.alloc(start.data(), L + 1); g.levelWeight = buf.alloc(ones.data(), L);
-  if (c.mean) g.mean = buf.alloc<double>(nullptr, L);
-  if (c.m2) g.m2 = buf.alloc<double>(nullptr, L);
-  g.S = r.S; g.L = (int64_t)L; g.statistic = 0; g.hasThreshold = 0; g.threshold = 0.0;
-  QuantileDev qd{};
-  if (Q) { qd.probs = buf.alloc(c.probs, Q); qd.quantiles = buf.alloc<double>(nullptr, Q * L); qd.nT = (int64_t)L; qd.S = r.S; qd.Q = c.Q; qd.Sp = Sp; qd.R = Rq; }
-  if (plan.staged) HIP_OK(hipFuncSetAttribute((const void*)k_predict_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-  if (Q) HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortLds));
+  LevelsSummary sum;          // D's 7 + T rows as levels of unit weight
+  sum.prepare(buf, cp, r.S, c.probs, c.Q, (int64_t)L);
+  double* mean = c.mean ? buf.alloc<double>(nullptr, L) : nullptr;
+  double* m2 = c.m2 ? buf.alloc<double>(nullptr, L) : nullptr;
+  double* quantiles = Q ? buf.alloc<double>(nullptr, Q * L) : nullptr;
+  predict_values_prepare(plan);
   if (T) {
     if (search) HIP_OK(hipFuncSetAttribute((const void*)k_check_reduce<0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)binLds));
     else HIP_OK(hipFuncSetAttribute((const void*)k_check_reduce<0, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)binLds));
   }
-  int64_t mine = 0;
-  for (int64_t ch = 0; ch < chunks; ++ch) {
+  LaunchCount launched{launches};
+  for (int64_t ch = 0; ch < cp.chunks; ++ch) {
     a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0);
-    const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
-    // segments of draws: quantile_run's rule
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
-    a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
-    const int segs = (int)((r.S + a.segDraws - 1) / a.segDraws);
-    if (plan.staged) hipLaunchKernelGGL(k_predict_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, a);
-    else hipLaunchKernelGGL(k_predict_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, a);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
+    predict_values_launch(stream, plan, chunk_grid(a), a); launched();
     p.row0 = a.chunk0; p.rows = a.chunkRows;
     const dim3 grid((unsigned)((p.rows + SP_SLAB - 1) / SP_SLAB), (unsigned)((r.S + SP_BLOCK - 1) / SP_BLOCK));
     if (link) hipLaunchKernelGGL((k_check_reduce<1, false, false>), grid, dim3(SP_BLOCK), 0, stream, p);
     else if (!T) hipLaunchKernelGGL((k_check_reduce<0, false, false>), grid, dim3(SP_BLOCK), 0, stream, p);
     else if (search) hipLaunchKernelGGL((k_check_reduce<0, true, true>), grid, dim3(SP_BLOCK), binLds, stream, p);
     else hipLaunchKernelGGL((k_check_reduce<0, true, false>), grid, dim3(SP_BLOCK), binLds, stream, p);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
+    launched();
     const int64_t m = r.S + (T ? (int64_t)(T + 1) * r.S : 0);
-    hipLaunchKernelGGL(k_check_fold, dim3((unsigned)std::min<int64_t>(GRID_MAX, (m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, p);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
+    hipLaunchKernelGGL(k_check_fold, dim3((unsigned)std::min<int64_t>(GRID_MAX, (m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, p); launched();
   }
-  hipLaunchKernelGGL(k_check_finish, dim3((unsigned)std::min<int64_t>(GRID_MAX, (r.S + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, p);
-  HIP_OK(hipGetLastError()); ++launches; ++mine;
-  if (c.mean || c.m2) {
-    hipLaunchKernelGGL(k_level_rows, dim3((unsigned)((L + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, stream, g);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
-  }
-  if (Q) {
-    qd.vals = p.out; qd.chunk0 = 0; qd.chunkRows = (int64_t)L;
-    hipLaunchKernelGGL(k_row_quantiles, dim3((unsigned)((qd.chunkRows + Rq - 1) / Rq)), dim3(QT_BLOCK), sortLds, stream, qd);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
-  }
-  if (c.mean) HIP_OK(hipMemcpyAsync(c.mean, g.mean, L * 8, hipMemcpyDeviceToHost, stream));
-  if (c.m2) HIP_OK(hipMemcpyAsync(c.m2, g.m2, L * 8, hipMemcpyDeviceToHost, stream));
-  if (Q) HIP_OK(hipMemcpyAsync(c.quantiles, qd.quantiles, Q * L * 8, hipMemcpyDeviceToHost, stream));
+  hipLaunchKernelGGL(k_check_finish, dim3((unsigned)std::min<int64_t>(GRID_MAX, (r.S + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, p); launched();
+  sum.run(stream, launched, p.out, (int64_t)L, 0, mean, m2, quantiles, (int64_t)L);
+  if (mean) HIP_OK(hipMemcpyAsync(c.mean, mean, L * 8, hipMemcpyDeviceToHost, stream));
+  if (m2) HIP_OK(hipMemcpyAsync(c.m2, m2, L * 8, hipMemcpyDeviceToHost, stream));
+  if (Q) HIP_OK(hipMemcpyAsync(c.quantiles, quantiles, Q * L * 8, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipMemcpyAsync(c.draws, p.out, L * S * 8, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
-  r.info[0] = plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = mine;
+  r.info[0] = plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = cp.chunks; r.info[3] = launched.mine;
   r.info[4] = buf.bytes; r.info[5] = r.S; r.info[6] = c.T; r.info[7] = c.zeroSlabs;
 }

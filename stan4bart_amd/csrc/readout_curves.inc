@@ -11,7 +11,7 @@
 //                           z_g = response_scale(f_g) + lin (k_partial_dependence's expression), v_g = z_g or readout_phi(z_g), c = v_g - v_a.
 //   anchor >= 0, link 0:    s_g = walk_trees(0.0; the affected trees under g), c = range_k (s_g - s_a): k_contrast_values' formula.  The unaffected trees and
 //                           the linear parts cancel: not walked, not uploaded.
-// Per chunk of C rows (C = scratch / (8 S G) in multiples of 64: curves_run) the scratch holds the chunk's curves row-major over the pseudo-rows (row, g):
+// Per chunk of C rows (chunk_plan with G values per row and draw: C = scratch / (8 S G) in multiples of 64) the scratch holds the chunk's curves row-major over the pseudo-rows (row, g):
 // vals[((r G) + g) S + k], so that k_row_quantiles and k_level_rows run over it UNCHANGED with C G rows.
 //   k_curve_values<STAGED, CANCEL>   k_contrast_values' loop (tiles of PS_BLOCK rows, blockIdx.y segments of draws, double-buffered stage_draw<true>) around
 //       k_partial_dependence's walk: base once per (row, draw), the affected trees per grid point.
@@ -28,7 +28,7 @@
 //                     k), keeps max, min and the LOWEST index of each (strict compares in ascending g), stores r(i,k) = max - min into base[r S + k] and
 //                     counts its indices in integer LDS counters; lane g then stores count / S.  No floating-point atomics anywhere.
 //   k_level_rows, k_row_quantiles   unchanged: over vals as C G levels / rows of unit weight (mean, m2, quantiles), over base as C rows (the range's).
-constexpr int64_t CV_SCRATCH_DEFAULT = (int64_t)512 << 20;   // value scratch of a chunk at most: G curves per row make quantile_run's 64 MiB a chunk of few tiles (DESIGN.md 5.16)
+constexpr int64_t CV_SCRATCH_DEFAULT = (int64_t)512 << 20;   // value scratch of a chunk at most: G curves per row make QT_SCRATCH_DEFAULT's 64 MiB a chunk of few tiles (DESIGN.md 5.16)
 constexpr int CV_BLOCK = 256;              // threads per workgroup of k_curve_rows
 constexpr int CV_SLAB = 64;                // rows per workgroup of k_curve_rows
 
@@ -154,26 +154,6 @@ static void curve_values_launch(hipStream_t stream, const ReadoutPlan& plan, dim
   } else hipLaunchKernelGGL((k_curve_values<false, CANCEL>), grid, dim3(PS_BLOCK), 0, stream, a);
 }
 
-// mean / m2 (k_level_rows) and quantiles (k_row_quantiles) of the n rows of `vals` [n x S], written at row `first` of the outputs — in pieces of at most
-// GP_SORT_LEVELS rows, for which `start` (0, 1, 2, ...) and `ones` are long enough
-static void curve_summaries(hipStream_t stream, GroupsDev g, QuantileDev qd, double* vals, int64_t n, int64_t first, double* mean, double* m2, bool sort,
-                            size_t sortLds, int64_t& launches, int64_t& mine) {
-  const int64_t S = g.S;
-  for (int64_t l0 = 0; l0 < n; l0 += GP_SORT_LEVELS) {
-    const int64_t L = std::min<int64_t>(GP_SORT_LEVELS, n - l0);
-    if (mean || m2) {
-      g.lev = vals + (size_t)l0 * (size_t)S; g.L = L; g.mean = mean ? mean + first + l0 : nullptr; g.m2 = m2 ? m2 + first + l0 : nullptr;
-      hipLaunchKernelGGL(k_level_rows, dim3((unsigned)std::min<int64_t>(GRID_MAX, (L + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, stream, g);
-      HIP_OK(hipGetLastError()); ++launches; ++mine;
-    }
-    if (sort) {
-      qd.vals = vals + (size_t)l0 * (size_t)S; qd.chunk0 = first + l0; qd.chunkRows = L;
-      hipLaunchKernelGGL(k_row_quantiles, dim3((unsigned)((L + qd.R - 1) / qd.R)), dim3(QT_BLOCK), sortLds, stream, qd);
-      HIP_OK(hipGetLastError()); ++launches; ++mine;
-    }
-  }
-}
-
 // uploads, per chunk the value kernel, k_curve_rows and the summary kernels, the downloads — on `stream`, everything allocated here freed here
 // (summary_run's discipline)
 static void curves_run(hipStream_t stream, int P, const CurvesCall& c, int64_t& launches) {
@@ -183,20 +163,11 @@ static void curves_run(hipStream_t stream, int P, const CurvesCall& c, int64_t& 
   if (!walks) r.route = 2;                                        // (nothing to stage)
   if (cancel) { r.offset = nullptr; r.M = 0; r.E = 0; }           // the linear parts cancel: not uploaded, not evaluated
   const ReadoutPlan plan = readout_plan(r, 0, 8, false);          // no reduction space; the workgroups are chosen per chunk
+  const ChunkPlan cp = chunk_plan(r.nT, r.S, c.scratchBytes, CV_SCRATCH_DEFAULT, c.G, 64);          // G values per row and draw; Sp and R are a draw row's
   CallBuffers buf(stream);
   const size_t nT = (size_t)r.nT, S = (size_t)r.S, Q = (size_t)c.Q, G = (size_t)c.G;
-  // rows per chunk: quantile_run's rule with G values per row and draw
-  const int64_t scratch = c.scratchBytes > 0 ? std::min(c.scratchBytes, CV_SCRATCH_DEFAULT) : CV_SCRATCH_DEFAULT;
-  const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(64, scratch / (8 * r.S * c.G) / 64 * 64));
-  const int64_t chunks = (r.nT + C - 1) / C;
-  int Sp = 1; while (Sp < r.S) Sp <<= 1;
-  const int R = std::max(1, QT_SORT / Sp);
-  const size_t sortLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT);
+  const int64_t C = cp.C;
   const bool perPoint = c.mean || c.m2 || Q, extremes = c.pMax || c.pMin || c.rangeMean || c.rangeM2 || c.rangeQuantiles;
-  const size_t piece = (size_t)std::min<int64_t>(GP_SORT_LEVELS, C * c.G);
-  std::vector<int64_t> start(piece + 1);
-  for (size_t l = 0; l <= piece; ++l) start[l] = (int64_t)l;
-  const std::vector<double> ones(piece, 1.0);
   CurvesDev a{};
   buf.upload_rows(a, r, P, plan.stageNodes);
   a.order = buf.alloc(c.order, S * (size_t)r.T);
@@ -207,48 +178,36 @@ static void curves_run(hipStream_t stream, int P, const CurvesCall& c, int64_t& 
   if (c.pMax) a.pMax = buf.alloc<double>(nullptr, nT * G);
   if (c.pMin) a.pMin = buf.alloc<double>(nullptr, nT * G);
   a.G = c.G; a.V = c.V; a.var0 = c.vars[0]; a.var1 = c.V > 1 ? c.vars[1] : -2; a.anchor = c.anchor;          // (-2: no node carries it)
-  a.Q = c.Q; a.Sp = Sp; a.R = R;
-  GroupsDev g{};
-  g.levelStart = buf.alloc(start.data(), piece + 1); g.levelWeight = buf.alloc(ones.data(), piece);
-  g.S = r.S; g.statistic = 0; g.hasThreshold = 0; g.threshold = 0.0;
+  a.Q = c.Q; a.Sp = cp.Sp; a.R = cp.R;
+  LevelsSummary sum;          // the chunk's C G curve rows, then its C range rows, as levels of unit weight
+  sum.prepare(buf, cp, r.S, c.probs, c.Q, C * c.G);
   double* mean = c.mean ? buf.alloc<double>(nullptr, nT * G) : nullptr;
   double* m2 = c.m2 ? buf.alloc<double>(nullptr, nT * G) : nullptr;
   double* rangeMean = c.rangeMean ? buf.alloc<double>(nullptr, nT) : nullptr;
   double* rangeM2 = c.rangeM2 ? buf.alloc<double>(nullptr, nT) : nullptr;
-  QuantileDev qd{}, qr{};          // the sort over the curves (n_test G rows) and over the ranges (n_test rows)
-  if (Q) {
-    qd.probs = buf.alloc(c.probs, Q); qd.quantiles = buf.alloc<double>(nullptr, Q * nT * G); qd.nT = r.nT * c.G; qd.S = r.S; qd.Q = c.Q; qd.Sp = Sp; qd.R = R;
-    qr = qd; qr.nT = r.nT;
-    if (c.rangeQuantiles) qr.quantiles = buf.alloc<double>(nullptr, Q * nT);
-    HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortLds));
-  }
-  int64_t mine = 0;
-  for (int64_t ch = 0; ch < chunks; ++ch) {
+  double* quantiles = Q ? buf.alloc<double>(nullptr, Q * nT * G) : nullptr;
+  double* rangeQuantiles = Q && c.rangeQuantiles ? buf.alloc<double>(nullptr, Q * nT) : nullptr;
+  LaunchCount launched{launches};
+  for (int64_t ch = 0; ch < cp.chunks; ++ch) {
     a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0);
-    const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
-    // segments of draws: quantile_run's rule
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
-    a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
-    const dim3 grid(wg, (unsigned)((r.S + a.segDraws - 1) / a.segDraws));
+    const dim3 grid = chunk_grid(a);
     if (cancel) curve_values_launch<true>(stream, plan, grid, a); else curve_values_launch<false>(stream, plan, grid, a);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
-    if (perPoint) curve_summaries(stream, g, qd, a.vals, a.chunkRows * c.G, a.chunk0 * c.G, mean, m2, Q > 0, sortLds, launches, mine);
+    launched();
+    if (perPoint) sum.run(stream, launched, a.vals, a.chunkRows * c.G, a.chunk0 * c.G, mean, m2, quantiles, r.nT * c.G);
     if (extremes) {
-      hipLaunchKernelGGL(k_curve_rows, dim3((unsigned)((a.chunkRows + CV_SLAB - 1) / CV_SLAB)), dim3(CV_BLOCK), 0, stream, a);
-      HIP_OK(hipGetLastError()); ++launches; ++mine;
-      if (rangeMean || rangeM2 || c.rangeQuantiles)
-        curve_summaries(stream, g, qr, a.base, a.chunkRows, a.chunk0, rangeMean, rangeM2, c.rangeQuantiles != nullptr, sortLds, launches, mine);
+      hipLaunchKernelGGL(k_curve_rows, dim3((unsigned)((a.chunkRows + CV_SLAB - 1) / CV_SLAB)), dim3(CV_BLOCK), 0, stream, a); launched();
+      if (rangeMean || rangeM2 || rangeQuantiles) sum.run(stream, launched, a.base, a.chunkRows, a.chunk0, rangeMean, rangeM2, rangeQuantiles, r.nT);
     }
   }
   if (mean) HIP_OK(hipMemcpyAsync(c.mean, mean, nT * G * 8, hipMemcpyDeviceToHost, stream));
   if (m2) HIP_OK(hipMemcpyAsync(c.m2, m2, nT * G * 8, hipMemcpyDeviceToHost, stream));
-  if (Q) HIP_OK(hipMemcpyAsync(c.quantiles, qd.quantiles, Q * nT * G * 8, hipMemcpyDeviceToHost, stream));
+  if (Q) HIP_OK(hipMemcpyAsync(c.quantiles, quantiles, Q * nT * G * 8, hipMemcpyDeviceToHost, stream));
   if (c.pMax) HIP_OK(hipMemcpyAsync(c.pMax, a.pMax, nT * G * 8, hipMemcpyDeviceToHost, stream));
   if (c.pMin) HIP_OK(hipMemcpyAsync(c.pMin, a.pMin, nT * G * 8, hipMemcpyDeviceToHost, stream));
   if (rangeMean) HIP_OK(hipMemcpyAsync(c.rangeMean, rangeMean, nT * 8, hipMemcpyDeviceToHost, stream));
   if (rangeM2) HIP_OK(hipMemcpyAsync(c.rangeM2, rangeM2, nT * 8, hipMemcpyDeviceToHost, stream));
-  if (c.rangeQuantiles) HIP_OK(hipMemcpyAsync(c.rangeQuantiles, qr.quantiles, Q * nT * 8, hipMemcpyDeviceToHost, stream));
+  if (rangeQuantiles) HIP_OK(hipMemcpyAsync(c.rangeQuantiles, rangeQuantiles, Q * nT * 8, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
-  r.info[0] = !walks ? 0 : plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = ((int64_t)R << 32) | (int64_t)Sp;
-  r.info[4] = r.maxDrawNodes; r.info[5] = mine; r.info[6] = buf.bytes; r.info[7] = (c.maxAffected << 32) | c.totalAffected;
+  r.info[0] = !walks ? 0 : plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = cp.chunks; r.info[3] = ((int64_t)cp.R << 32) | (int64_t)cp.Sp;
+  r.info[4] = r.maxDrawNodes; r.info[5] = launched.mine; r.info[6] = buf.bytes; r.info[7] = (c.maxAffected << 32) | c.totalAffected;
 }

@@ -173,26 +173,17 @@ static void projection_run(hipStream_t stream, int P, const ProjectionCall& c, i
   bool walks = true;
   SummaryCall r = two ? contrast_rows(ar, walks) : ar.rows;
   const ReadoutPlan plan = readout_plan(r, 0, two ? 8 : 4, false);
+  const ChunkPlan cp = chunk_plan(r.nT, r.S, ar.scratchBytes, QT_SCRATCH_DEFAULT, 1, PJ_SLAB);          // whole slabs
   CallBuffers buf(stream);
   const size_t nT = (size_t)r.nT, S = (size_t)r.S, Q = (size_t)ar.Q, K = (size_t)c.K, L = K + 1;
   const int KT = c.K <= 8 ? 8 : c.K <= 16 ? 16 : 32;
-  // rows per chunk: quantile_run's rule, in whole slabs of PJ_SLAB rows
-  const int64_t scratch = ar.scratchBytes > 0 ? std::min(ar.scratchBytes, QT_SCRATCH_DEFAULT) : QT_SCRATCH_DEFAULT;
-  const int64_t C = std::min<int64_t>(r.nT, std::max<int64_t>(PJ_SLAB, scratch / (8 * r.S) / PJ_SLAB * PJ_SLAB));
-  const int64_t chunks = (r.nT + C - 1) / C;
-  const int64_t slabsMax = (C + PJ_SLAB - 1) / PJ_SLAB;
-  int Sp = 1; while (Sp < r.S) Sp <<= 1;
-  const int R = std::max(1, QT_SORT / Sp);
-  const size_t sortLds = (size_t)8 * (size_t)std::max(Sp, QT_SORT);
+  const int64_t C = cp.C, slabsMax = (C + PJ_SLAB - 1) / PJ_SLAB;
   // the design in rows of KT doubles, zero-filled
   std::vector<double> padded;
   if ((int)K != KT) {
     padded.assign(nT * (size_t)KT, 0.0);
     for (size_t i = 0; i < nT; ++i) std::copy(c.design + i * K, c.design + (i + 1) * K, padded.begin() + i * (size_t)KT);
   }
-  std::vector<int64_t> start(L + 1);
-  for (size_t l = 0; l <= L; ++l) start[l] = (int64_t)l;
-  const std::vector<double> ones(L, 1.0);
   ContrastDev a{};
   if (two) contrast_upload(buf, a, ar, r, P, plan); else buf.upload_rows(a, r, P, plan.stageNodes);
   a.vals = buf.alloc<double>(nullptr, (size_t)C * S);
@@ -205,67 +196,45 @@ static void projection_run(hipStream_t stream, int P, const ProjectionCall& c, i
   double* mom = buf.alloc<double>(nullptr, (K + 2) * S);
   ProjSolveDev sv{};
   sv.gram = gram; sv.mom = mom; sv.out = buf.alloc<double>(nullptr, L * S);
-  sv.levelStart = buf.alloc(start.data(), L + 1); sv.flag = buf.alloc<int64_t>(nullptr, 1);
+  sv.flag = buf.alloc<int64_t>(nullptr, 1);
   sv.S = r.S; sv.K = c.K; sv.W = c.W; sv.tol = c.tol;
-  GroupsDev g{};
-  g.lev = sv.out; g.levelStart = sv.levelStart; g.levelWeight = buf.alloc(ones.data(), L);
+  LevelsSummary sum;          // the matrix's K + 1 rows as levels of unit weight, whose starts the solve empties where the design is deficient
+  sum.prepare(buf, cp, r.S, ar.probs, ar.Q, (int64_t)L);
+  sv.levelStart = const_cast<int64_t*>(sum.g.levelStart);
+  GroupsDev& g = sum.g;       // a threshold and pAbove beside mean and m2: k_level_rows is launched here, over the matrix at once
+  g.lev = sv.out; g.L = (int64_t)L; g.hasThreshold = c.hasThreshold; g.threshold = c.threshold;
   if (c.mean) g.mean = buf.alloc<double>(nullptr, L);
   if (c.m2) g.m2 = buf.alloc<double>(nullptr, L);
   if (c.pAbove) g.pAbove = buf.alloc<double>(nullptr, L);
-  g.S = r.S; g.L = (int64_t)L; g.statistic = 0; g.hasThreshold = c.hasThreshold; g.threshold = c.threshold;
-  QuantileDev qd{};
-  if (Q) { qd.probs = buf.alloc(ar.probs, Q); qd.quantiles = buf.alloc<double>(nullptr, Q * L); qd.nT = (int64_t)L; qd.S = r.S; qd.Q = ar.Q; qd.Sp = Sp; qd.R = R; }
-  if (plan.staged) {
-    if (two) HIP_OK(hipFuncSetAttribute((const void*)k_contrast_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-    else HIP_OK(hipFuncSetAttribute((const void*)k_predict_values<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
-  }
-  if (Q) HIP_OK(hipFuncSetAttribute((const void*)k_row_quantiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortLds));
-  int64_t mine = 0;
+  double* quantiles = Q ? buf.alloc<double>(nullptr, Q * L) : nullptr;
+  arm_values_prepare(plan, two);
+  LaunchCount launched{launches};
   // the reduce and the fold of one piece of rows: p.src, p.ld, p.cols, p.tot, p.row0, p.rows, p.first are set
   auto moments = [&]() {
     const dim3 grid((unsigned)((p.rows + PJ_SLAB - 1) / PJ_SLAB), (unsigned)((p.cols + PJ_BLOCK - 1) / PJ_BLOCK));
     if (KT == 8) hipLaunchKernelGGL(k_proj_reduce<8>, grid, dim3(PJ_BLOCK), 0, stream, p);
     else if (KT == 16) hipLaunchKernelGGL(k_proj_reduce<16>, grid, dim3(PJ_BLOCK), 0, stream, p);
     else hipLaunchKernelGGL(k_proj_reduce<32>, grid, dim3(PJ_BLOCK), 0, stream, p);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
+    launched();
     const int64_t m = (int64_t)(p.K + 2) * p.cols;
-    hipLaunchKernelGGL(k_proj_fold, dim3((unsigned)std::min<int64_t>(GRID_MAX, (m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, p);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
+    hipLaunchKernelGGL(k_proj_fold, dim3((unsigned)std::min<int64_t>(GRID_MAX, (m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, p); launched();
   };
   // G, once per call: the design's own columns as the values, in the pieces the chunks are
-  for (int64_t ch = 0; ch < chunks; ++ch) {
+  for (int64_t ch = 0; ch < cp.chunks; ++ch) {
     p.row0 = ch * C; p.rows = std::min<int64_t>(C, r.nT - p.row0); p.first = ch == 0;
     p.src = p.design + (size_t)p.row0 * (size_t)KT; p.ld = KT; p.cols = c.K; p.tot = gram;
     moments();
   }
-  for (int64_t ch = 0; ch < chunks; ++ch) {
+  for (int64_t ch = 0; ch < cp.chunks; ++ch) {
     a.chunk0 = ch * C; a.chunkRows = std::min<int64_t>(C, r.nT - a.chunk0);
-    const int wg = (int)std::min<int64_t>((a.chunkRows + PS_BLOCK - 1) / PS_BLOCK, PS_GRID_MAX);
-    // segments of draws: quantile_run's rule
-    const int64_t want = std::max<int64_t>(1, std::min<int64_t>((QT_FILL + wg - 1) / wg, r.S / QT_SEG_MIN));
-    a.segDraws = ((r.S + want - 1) / want + QT_GROUP - 1) / QT_GROUP * QT_GROUP;
-    const int segs = (int)((r.S + a.segDraws - 1) / a.segDraws);
-    if (two) {
-      if (plan.staged) hipLaunchKernelGGL(k_contrast_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, a);
-      else hipLaunchKernelGGL(k_contrast_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, a);
-    } else {
-      if (plan.staged) hipLaunchKernelGGL(k_predict_values<true>, dim3(wg, segs), dim3(PS_BLOCK), plan.lds, stream, (QuantileDev)a);
-      else hipLaunchKernelGGL(k_predict_values<false>, dim3(wg, segs), dim3(PS_BLOCK), 0, stream, (QuantileDev)a);
-    }
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
+    arm_values_launch(stream, plan, chunk_grid(a), a, two); launched();
     p.row0 = a.chunk0; p.rows = a.chunkRows; p.first = ch == 0;
     p.src = a.vals; p.ld = r.S; p.cols = r.S; p.tot = mom;
     moments();
   }
-  hipLaunchKernelGGL(k_proj_solve, dim3((unsigned)std::min<int64_t>(GRID_MAX, (r.S + PJ_SOLVE_BLOCK - 1) / PJ_SOLVE_BLOCK)), dim3(PJ_SOLVE_BLOCK), 0, stream, sv);
-  HIP_OK(hipGetLastError()); ++launches; ++mine;
-  hipLaunchKernelGGL(k_level_rows, dim3((unsigned)((L + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, stream, g);
-  HIP_OK(hipGetLastError()); ++launches; ++mine;
-  if (Q) {
-    qd.vals = sv.out; qd.chunk0 = 0; qd.chunkRows = (int64_t)L;
-    hipLaunchKernelGGL(k_row_quantiles, dim3((unsigned)((qd.chunkRows + R - 1) / R)), dim3(QT_BLOCK), sortLds, stream, qd);
-    HIP_OK(hipGetLastError()); ++launches; ++mine;
-  }
+  hipLaunchKernelGGL(k_proj_solve, dim3((unsigned)std::min<int64_t>(GRID_MAX, (r.S + PJ_SOLVE_BLOCK - 1) / PJ_SOLVE_BLOCK)), dim3(PJ_SOLVE_BLOCK), 0, stream, sv); launched();
+  hipLaunchKernelGGL(k_level_rows, dim3((unsigned)((L + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, stream, g); launched();
+  if (Q) sum.run(stream, launched, sv.out, (int64_t)L, 0, nullptr, nullptr, quantiles, (int64_t)L);
   int64_t flag = 0;
   HIP_OK(hipMemcpyAsync(c.coef, sv.out, K * S * 8, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipMemcpyAsync(c.r2, sv.out + K * S, S * 8, hipMemcpyDeviceToHost, stream));
@@ -273,9 +242,9 @@ static void projection_run(hipStream_t stream, int P, const ProjectionCall& c, i
   if (c.mean) HIP_OK(hipMemcpyAsync(c.mean, g.mean, L * 8, hipMemcpyDeviceToHost, stream));
   if (c.m2) HIP_OK(hipMemcpyAsync(c.m2, g.m2, L * 8, hipMemcpyDeviceToHost, stream));
   if (c.pAbove) HIP_OK(hipMemcpyAsync(c.pAbove, g.pAbove, L * 8, hipMemcpyDeviceToHost, stream));
-  if (Q) HIP_OK(hipMemcpyAsync(c.quantiles, qd.quantiles, Q * L * 8, hipMemcpyDeviceToHost, stream));
+  if (Q) HIP_OK(hipMemcpyAsync(c.quantiles, quantiles, Q * L * 8, hipMemcpyDeviceToHost, stream));
   HIP_OK(hipStreamSynchronize(stream));
-  r.info[0] = !walks ? 0 : plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = chunks; r.info[3] = mine;
+  r.info[0] = !walks ? 0 : plan.staged ? 1 : 2; r.info[1] = C; r.info[2] = cp.chunks; r.info[3] = launched.mine;
   r.info[4] = buf.bytes; r.info[5] = r.S; r.info[6] = flag; r.info[7] = c.K;
 }
 

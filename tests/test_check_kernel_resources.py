@@ -67,7 +67,10 @@ def test_check_kernels_are_included_after_the_spread_kernels_and_share_their_rou
     assert not re.search(r"\w*[aA]tomic\w*\s*\(", text), "readout_check.inc calls an atomic function"
     for k in ("k_check_reduce", "k_check_fold", "k_check_finish"):
         assert f"void {k}(" in text
-    assert "k_predict_values<" in text and "k_level_rows" in text and "k_row_quantiles" in text
+    # the value kernel, the chunk rule and the summary over the draws (k_level_rows, k_row_quantiles) are called through the shared helpers
+    code = "\n".join(line.split("//")[0] for line in text.splitlines())
+    for used in ("chunk_plan(", "chunk_grid(", "predict_values_prepare(", "predict_values_launch(", "LevelsSummary sum;", "sum.prepare(", "sum.run("):
+        assert used in code, used
     # the value kernel, the summary kernels and the bin routine are used, not copied
     assert "void k_level_rows(" not in text and "void k_row_quantiles(" not in text and "void k_predict_values(" not in text
     assert "sp_bins<SEARCH, CK_AHEAD>(" in text and "void sp_bins(" not in text

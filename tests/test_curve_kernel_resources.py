@@ -68,8 +68,8 @@ def test_curve_kernels_are_included_last_and_share_the_family_routines():
     for k in ("k_curve_values", "k_curve_rows"):
         assert f"void {k}(" in text
     # the walk, the staging, the summary kernels are used, not copied
-    for used in ("walk_trees<STAGED, true, true>(", "walk_trees<STAGED, false, true>(", "stage_draw<true>(", "add_linear(", "readout_phi(", "k_level_rows", "k_row_quantiles",
-                 "readout_plan("):
+    for used in ("walk_trees<STAGED, true, true>(", "walk_trees<STAGED, false, true>(", "stage_draw<true>(", "add_linear(", "readout_phi(", "readout_plan(",
+                 "chunk_plan(", "chunk_grid(", "LevelsSummary sum;", "sum.prepare(", "sum.run("):          # (k_level_rows, k_row_quantiles: through LevelsSummary)
         assert used in code, used
     for copied in ("void k_level_rows(", "void k_row_quantiles(", "double walk_trees(", "void stage_draw(", "void qt_sort_rows("):
         assert copied not in text, copied

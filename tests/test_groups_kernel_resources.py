@@ -59,4 +59,8 @@ def test_level_kernels_are_the_last_include_of_the_main_unit():
     assert not re.search(r"\w*[aA]tomic\w*\s*\(", text), "dev_groups.inc calls an atomic function"
     for k in KERNELS:
         assert f"void {k}(" in text
-    assert "k_predict_values<" in text and "k_contrast_values<" in text and "k_row_quantiles" in text and "qt_sort_rows" not in text
+    # the value kernels of either arm, the chunk rule and the sort (k_row_quantiles) are called through the shared helpers
+    code = "\n".join(line.split("//")[0] for line in text.splitlines())
+    for used in ("chunk_plan(", "chunk_grid(", "arm_values_prepare(", "arm_values_launch(", "row_quantiles_prepare(", "row_quantiles_launch(", "sum.prepare(", "sum.run("):
+        assert used in code, used
+    assert "qt_sort_rows" not in text

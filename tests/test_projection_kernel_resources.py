@@ -63,6 +63,10 @@ def test_projection_kernels_are_included_after_the_level_kernels():
     assert not re.search(r"\w*[aA]tomic\w*\s*\(", text), "readout_projection.inc calls an atomic function"
     for k in ("k_proj_reduce", "k_proj_fold", "k_proj_solve"):
         assert f"void {k}(" in text
-    assert "k_predict_values<" in text and "k_contrast_values<" in text and "k_level_rows" in text and "k_row_quantiles" in text
+    # the value kernels of either arm, the chunk rule and the sort (k_row_quantiles) are called through the shared helpers; k_level_rows is launched here
+    code = "\n".join(line.split("//")[0] for line in text.splitlines())
+    for used in ("chunk_plan(", "chunk_grid(", "arm_values_prepare(", "arm_values_launch(", "LevelsSummary sum;", "sum.prepare(", "sum.run(",
+                 "hipLaunchKernelGGL(k_level_rows, "):
+        assert used in code, used
     # the summary kernels are used, not copied
     assert "void k_level_rows(" not in text and "void k_row_quantiles(" not in text

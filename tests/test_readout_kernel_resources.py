@@ -75,3 +75,28 @@ def test_sort_kernel_uses_no_private_memory(usage):
     u = usage["sort", None]
     assert u["spill"] == 0 and u["scratch"] == 0, f"k_row_quantiles uses private memory: {u}"
     assert u["lds"] == 0, u                 # dynamic: 8 x max(padded draws, 4096) bytes
+
+
+def test_the_chunk_rule_and_the_value_launches_are_written_once():
+    """The host side of a chunked read-out: rows per chunk, segments of draws and the launches of the two value kernels stand in the file
+    that owns the kernel and nowhere else under csrc — a read-out calls chunk_plan, chunk_grid and the launch helpers.  Source text with the comments
+    stripped; nothing is compiled."""
+    code = {}
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith((".inc", ".hip", ".hpp")):
+            with open(os.path.join(CSRC, name)) as f:
+                code[name] = "\n".join(line.split("//")[0] for line in f.read().splitlines())
+
+    def files_with(pattern):
+        return sorted(n for n, c in code.items() if re.search(pattern, c))
+
+    # the deciding expressions of the rule: the filling of the device, the least segment, the scratch over 8 bytes per value, whole multiples of rows
+    for pattern in (r"\bQT_FILL\b", r"\bQT_SEG_MIN\b", r"scratch / \(8 \*", r"/ multiple \* multiple\b", r"scratchBytes > 0 \?"):
+        assert files_with(pattern) == ["dev_quantile.inc"], (pattern, files_with(pattern))
+    q = code["dev_quantile.inc"]
+    assert len(re.findall(r"scratch / \(8 \*", q)) == 1 and len(re.findall(r"\bQT_SEG_MIN\b", q)) == 2 and len(re.findall(r"\bQT_FILL\b", q)) == 2          # the constant and its one use
+    assert "scratch / (8 * S * perRowDraw) / multiple * multiple" in q
+    # the launches of the value kernels
+    assert files_with(r"hipLaunchKernelGGL\(k_predict_values<") == ["dev_quantile.inc"]
+    assert files_with(r"hipLaunchKernelGGL\(k_contrast_values<") == ["dev_contrast.inc"]
+    assert len(re.findall(r"hipLaunchKernelGGL\(k_predict_values<", q)) == 2 and len(re.findall(r"hipLaunchKernelGGL\(k_contrast_values<", code["dev_contrast.inc"])) == 2

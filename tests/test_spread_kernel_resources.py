@@ -63,7 +63,10 @@ def test_spread_kernels_are_included_after_the_projection_kernels():
     assert not re.search(r"\w*[aA]tomic\w*\s*\(", text), "readout_spread.inc calls an atomic function"
     for k in ("k_spread_reduce", "k_spread_fold", "k_spread_finish"):
         assert f"void {k}(" in text
-    assert "k_predict_values<" in text and "k_contrast_values<" in text and "k_level_rows" in text and "k_row_quantiles" in text
+    # the value kernels of either arm, the chunk rule and the summary over the draws (k_level_rows, k_row_quantiles) are called through the shared helpers
+    code = "\n".join(line.split("//")[0] for line in text.splitlines())
+    for used in ("chunk_plan(", "chunk_grid(", "arm_values_prepare(", "arm_values_launch(", "LevelsSummary sum;", "sum.prepare(", "sum.run("):
+        assert used in code, used
     # the summary kernels are used, not copied
     assert "void k_level_rows(" not in text and "void k_row_quantiles(" not in text
     assert "hipFuncAttributeMaxDynamicSharedMemorySize" in text and "extern __shared__" in text
