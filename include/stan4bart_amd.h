@@ -965,9 +965,14 @@ int S4B_FN(get_nuts_stats)(s4b_sampler* s, double out[4]);
 /* extension: run-ahead helpers of the NUTS transition.  The leapfrog states of a transition are a function of its start point, momentum draw,
  * step size and metric alone; a helper thread integrates one direction ahead while the sampler's thread builds the tree and consumes the
  * finished states in the order the doublings ask for them; a state the helper has not finished when it is asked for is computed by the
- * sampler's thread itself, as without a helper.  The chain is the same bit for bit with and without helpers.  n = 0: none; 1 (default): the
+ * sampler's thread itself, as without a helper.  The chain is the same bit for bit with and without helpers.  n = 0: none; 1: the
  * backward direction; 2: both directions.  (TEST HOOK, not part of the contract and not reachable through the environment: n + 16 makes the
- * sampler's thread wait for a helper's state instead of computing it, so that a test sees every state of a helper's direction come from the helper.)  The default is taken from the environment variable S4B_NUTS_HELPERS at create.
+ * sampler's thread wait for a helper's state instead of computing it, so that a test sees every state of a helper's direction come from the helper.)
+ * The default is the environment variable S4B_NUTS_HELPERS at create (0 / 1 / 2).  Where that is unset and this function is not called, the count is
+ * automatic: one helper, and a second one for the forward direction as long as the CPUs a helper of the sampler's thread can be put on (same
+ * last-level cache, another core, allowed to the process) span at least two cores, the CPUs the process may use span at least three cores for
+ * every live sampler that may run ahead, and the process's helper budget has room.  Cores, not hardware threads: a single chain with eight cores
+ * gets both helpers, a rank bound to two cores keeps one whether or not the cores have two hardware threads each.
  * Helpers exist only for a model whose gradient is closed-form host arithmetic (normal or flat coefficient prior, at most two coefficients per
  * grouping term) in hmc_mode 0; every other sampler integrates inline whatever n says.  A process has at most 8 helper threads in all; a
  * sampler that gets none integrates inline, and so does one whose thread may use no core but its own (a process bound to one core).  On Linux a

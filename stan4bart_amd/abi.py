@@ -804,7 +804,8 @@ class Sampler:
         return dict(transitions=int(out[0]), sum_treedepth=int(out[1]), sum_n_leapfrog=int(out[2]), divergent=int(out[3]))
 
     def set_nuts_helpers(self, n: int, wait: bool = False) -> None:
-        """Run-ahead helper threads of the NUTS transition: 0 none, 1 the backward direction (default), 2 both.  Same chain either way.
+        """Run-ahead helper threads of the NUTS transition: 0 none, 1 the backward direction, 2 both (never called and S4B_NUTS_HELPERS unset: 1, and 2 where
+        the process has the cores for it).  Same chain either way.
         wait (a test hook, not for use): the sampler's thread waits for a state its helper has not finished instead of computing it itself."""
         self._check(self._f("set_nuts_helpers")(self._h, int(n) | (16 if wait and n else 0)))
 

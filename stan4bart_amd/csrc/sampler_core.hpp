@@ -413,8 +413,9 @@ class SamplerCore {
     nc.init_buffer = sc->adapt_init_buffer; nc.term_buffer = sc->adapt_term_buffer; nc.window = sc->adapt_window;
     nc.stepsize = sc->stepsize; nc.jitter = sc->stepsize_jitter; nc.max_depth = sc->max_treedepth;
     nuts_.reset(new Nuts(*model_, nc, 1, warmup_));
-    // run-ahead helpers of the NUTS transition (stan_host.hpp Nuts::RunAhead): one by default, S4B_NUTS_HELPERS = 0 / 1 / 2 (more: 2, negative: 0)
-    { const char* e = std::getenv("S4B_NUTS_HELPERS"); const int n = e && *e ? std::atoi(e) : 1; nuts_->set_helpers(n < 0 ? 0 : (n > 2 ? 2 : n)); }
+    // run-ahead helpers of the NUTS transition (stan_host.hpp Nuts::RunAhead): S4B_NUTS_HELPERS = 0 / 1 / 2 (more: 2, negative: 0); unset: one, and a
+    // second one where the process has the cores for it (Nuts::set_helpers_auto)
+    { const char* e = std::getenv("S4B_NUTS_HELPERS"); if (e && *e) { const int n = std::atoi(e); nuts_->set_helpers(n < 0 ? 0 : (n > 2 ? 2 : n)); } else nuts_->set_helpers_auto(); }
     sync_runahead();
     row_.assign((size_t)(7 + model_->sp.n_constrained), 0.0);
 

@@ -950,6 +950,9 @@ inline bool runahead_budget_take() {
   return false;
 }
 inline void runahead_budget_give() { runahead_budget().fetch_add(1, std::memory_order_relaxed); }
+// samplers of the process that are alive and may run ahead (helpers wanted, a model and likelihood that allow them): the automatic helper count
+// grants a second helper only where the process may use three cores for each of them
+inline std::atomic<int>& runahead_live() { static std::atomic<int> n{0}; return n; }
 
 // Where a helper runs decides what a hand-over costs: a finished state is seven cache lines that cross from the helper's core to the sampler's.
 // Between cores under one last-level cache that is a few tens of nanoseconds, hidden behind the tree builder's own work; between cores of
@@ -980,13 +983,30 @@ struct CpuNeighbours {
   // ANYWHERE: no advice (no topology to read, or no such core: the scheduler decides); NOWHERE: the thread may use no core but its own (it is
   // bound to one core, as one-core-per-rank launchers do) — a helper would only take turns with it on that core, so the sampler runs without.
   // *domain: the CPUs under the last-level cache of `cpu` (the advice holds while the thread stays on them).
+  // *neighbourCores (may be NULL): how many cores the CPUs of *out belong to where they are such neighbours (same last-level cache, another core,
+  // allowed), 0 where there is no such advice; *allowedCores (may be NULL): how many cores the CPUs the thread may use belong to (0: unknown).  Cores,
+  // not hardware threads: two helpers on the two threads of one core would share it.  The automatic helper count goes by both.
   enum Advice { PLACE, ANYWHERE, NOWHERE };
-  static Advice helper_set(int cpu, cpu_set_t* out, cpu_set_t* domain) {
+  // the cores the CPUs of a set belong to (one read of a sibling list per core; a CPU whose list cannot be read is a core of its own)
+  static int count_cores(const cpu_set_t* set) {
+    cpu_set_t seen, sib; CPU_ZERO(&seen);
+    int cores = 0;
+    for (int c = 0; c < CPU_SETSIZE; ++c) {
+      if (!CPU_ISSET(c, set) || CPU_ISSET(c, &seen)) continue;
+      ++cores; CPU_SET(c, &seen);
+      if (read_list("/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", c, &sib)) CPU_OR(&seen, &seen, &sib);
+    }
+    return cores;
+  }
+  static Advice helper_set(int cpu, cpu_set_t* out, cpu_set_t* domain, int* neighbourCores = nullptr, int* allowedCores = nullptr) {
     cpu_set_t l3, smt, allowed;
     CPU_ZERO(domain); CPU_ZERO(out);
+    if (neighbourCores) *neighbourCores = 0;
+    if (allowedCores) *allowedCores = 0;
     if (cpu < 0 || cpu >= CPU_SETSIZE) return ANYWHERE;
     CPU_SET(cpu, domain);
     if (sched_getaffinity(0, sizeof allowed, &allowed) != 0) return ANYWHERE;
+    if (allowedCores) *allowedCores = count_cores(&allowed);
     if (!read_list("/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", cpu, &smt)) { CPU_ZERO(&smt); CPU_SET(cpu, &smt); }
     int others = 0;
     for (int c = 0; c < CPU_SETSIZE; ++c) if (CPU_ISSET(c, &allowed) && !CPU_ISSET(c, &smt)) ++others;
@@ -995,8 +1015,8 @@ struct CpuNeighbours {
     *domain = l3; CPU_SET(cpu, domain);
     int n = 0;
     for (int c = 0; c < CPU_SETSIZE; ++c) if (CPU_ISSET(c, &l3) && CPU_ISSET(c, &allowed) && !CPU_ISSET(c, &smt)) { CPU_SET(c, out); ++n; }
-    if (n > 0) return PLACE;
-    *out = allowed;           // (another cache domain is all there is: anywhere the thread itself may run)
+    if (n > 0) { if (neighbourCores) *neighbourCores = count_cores(out); return PLACE; }
+    *out = allowed;          // (another cache domain is all there is: anywhere the thread itself may run)
     return PLACE;
   }
 };
@@ -1137,12 +1157,17 @@ class Nuts {
   };
   // how many helpers this sampler may use (0, 1: the backward direction, 2: both), and whether its model and likelihood allow any: the owner
   // says so (closed-form gradient, Gram-form likelihood, no gradient check).  Helpers are created at the first transition that can use them.
-  void set_helpers(int n, bool wait = false) { helpersWanted_ = n < 0 ? 0 : (n > 2 ? 2 : n); helpersWait_ = wait; drop_helpers(helpersWanted_); }
-  void set_runahead_allowed(bool ok) { runaheadAllowed_ = ok; if (!ok) drop_helpers(0); }
+  void set_helpers(int n, bool wait = false) { helpersWanted_ = n < 0 ? 0 : (n > 2 ? 2 : n); helpersAuto_ = false; helpersWait_ = wait; drop_helpers(helpersWanted_); count_live(); }
+  // nobody has said how many: one helper, and a second one (the forward direction) where the cores are there for it — the CPUs a helper of this
+  // thread can be put on (CpuNeighbours::helper_set) span at least two cores, the CPUs the process may use span at least three cores for every
+  // live sampler that may run ahead, and the process's helper budget has room.  Looked at again at every transition (two counts kept from the last
+  // look at the topology and one atomic load).
+  void set_helpers_auto() { helpersWanted_ = 1; helpersAuto_ = true; helpersWait_ = false; count_live(); }
+  void set_runahead_allowed(bool ok) { runaheadAllowed_ = ok; if (!ok) drop_helpers(0); count_live(); }
   // {leapfrogs taken from a helper, leapfrogs of a helper's direction it had not finished in time (done by this thread itself; in wait mode:
   // waited for, and counted under "taken" as well), leapfrogs a helper computed that nobody took, transitions without a helper}
   void runahead_counters(int64_t out[4]) const { for (int i = 0; i < 4; ++i) out[i] = raCount_[i]; }
-  ~Nuts() { drop_helpers(0); }
+  ~Nuts() { drop_helpers(0); runaheadAllowed_ = false; count_live(); }
 
   Nuts(HostModel& m, const NutsControl& c, unsigned chain, int num_warmup) : model_(m), D_(m.sp.D), skip_(c.skip) {
     rng_.create(c.seed, chain);
@@ -1239,40 +1264,60 @@ class Nuts {
   int helpersWanted_ = 0; bool runaheadAllowed_ = false, vec_ = false, helpersWait_ = false;
   int64_t raPos_[2] = {0, 0}; bool raGradStale_[2] = {false, false};       // per direction: steps done in this transition; z_.g is older than z_.q
   int64_t raCount_[4] = {0, 0, 0, 0};
+  bool helpersAuto_ = false, live_ = false;
+  // this sampler among the live samplers of the process that may run ahead (runahead_live)
+  void count_live() {
+    const bool now = runaheadAllowed_ && helpersWanted_ > 0;
+    if (now != live_) { runahead_live().fetch_add(now ? 1 : -1, std::memory_order_relaxed); live_ = now; }
+  }
   void drop_helpers(int keep) {
     for (int k = 1; k >= keep && k >= 0; --k) if (ra_[k]) { ra_[k].reset(); runahead_budget_give(); }
+  }
+  // how many helpers the coming transition may have
+  int helpers_granted() const {
+    if (!helpersAuto_) return helpersWanted_;
+    return (nbrCores_ >= 2 && allowedCores_ >= 3 * std::max(1, runahead_live().load(std::memory_order_relaxed))) ? 2 : 1;
   }
   void ensure_helpers() {
     // (an array of 2^max_depth states per helper: a model with very many coefficients integrates inline)
     const size_t cap = (size_t)1 << max_depth_;
     if (max_depth_ > 20 || cap * ((size_t)3 * D_ + 1) * sizeof(double) > ((size_t)64 << 20)) return;
-    for (int k = 0; k < helpersWanted_; ++k) {
+    const int want = helpers_granted();
+    if (want < 2 && ra_[1]) drop_helpers(want);        // (the automatic count: more samplers or fewer cores than when the second helper was granted)
+    for (int k = 0; k < want; ++k) {
       if (ra_[k]) continue;
       if (!runahead_budget_take()) return;
       try { ra_[k].reset(new RunAhead(model_, D_, cap)); } catch (...) { runahead_budget_give(); return; }   // (no thread to be had: inline)
-      placed_ = false;
+      unplaced_ = true;
     }
   }
   // the helpers follow the sampler's thread from one last-level cache to the next (looked at once per transition; the CPU number comes without
   // a system call, the topology is read again only when the thread has moved to another CPU)
-  bool placed_ = false, noRoom_ = false;
+  bool placed_ = false, noRoom_ = false, unplaced_ = false, haveSet_ = false;
+  int nbrCores_ = 0, allowedCores_ = 0;       // of the last look: cores a helper can be put on, cores the thread may use
 #if defined(__linux__)
-  cpu_set_t placedDomain_;
+  cpu_set_t placedDomain_, placedSet_;
 #endif
-  // false: the thread has no core but its own to put a helper on; this transition runs without
-  bool place_helpers() {
+  // where the thread is now, before the helpers of the transition are chosen (the automatic count goes by what is found here).  false: it has
+  // no core but its own to put a helper on; this transition runs without
+  bool look_around() {
 #if defined(__linux__)
     const int cpu = sched_getcpu();
     if (cpu < 0 || cpu >= CPU_SETSIZE) return true;
     if (placed_ && CPU_ISSET(cpu, &placedDomain_)) return !noRoom_;        // still under the same last-level cache, same helpers
-    cpu_set_t set;
-    const CpuNeighbours::Advice advice = CpuNeighbours::helper_set(cpu, &set, &placedDomain_);
-    placed_ = true; noRoom_ = advice == CpuNeighbours::NOWHERE;
-    if (advice == CpuNeighbours::PLACE) for (int k = 0; k < 2; ++k) if (ra_[k]) ra_[k]->place_on(set);
+    const CpuNeighbours::Advice advice = CpuNeighbours::helper_set(cpu, &placedSet_, &placedDomain_, &nbrCores_, &allowedCores_);
+    placed_ = true; noRoom_ = advice == CpuNeighbours::NOWHERE; haveSet_ = advice == CpuNeighbours::PLACE; unplaced_ = true;
     return !noRoom_;
 #else
     return true;
 #endif
+  }
+  // after ensure_helpers(): helpers that are new, or whose thread has moved, go where the last look said
+  void place_helpers() {
+#if defined(__linux__)
+    if (unplaced_ && haveSet_) for (int k = 0; k < 2; ++k) if (ra_[k]) ra_[k]->place_on(placedSet_);
+#endif
+    unplaced_ = false;
   }
   // ends the helpers' work on the transition on every way out of it
   struct RunAheadScope {
@@ -1421,8 +1466,9 @@ class Nuts {
     RunAheadScope scope{*this};
     raPos_[0] = raPos_[1] = 0; raGradStale_[0] = raGradStale_[1] = false;
     if (runaheadAllowed_ && helpersWanted_ > 0) {
+      const bool room = look_around();
       ensure_helpers();
-      const bool room = place_helpers();
+      place_helpers();
       if (room && ra_[0]) { ra_[0]->start(z_, -eps_, inv_metric_, vec_); raDir_[0] = ra_[0].get(); }
       if (room && ra_[1]) { ra_[1]->start(z_, eps_, inv_metric_, vec_); raDir_[1] = ra_[1].get(); }
     }
