@@ -750,6 +750,59 @@ typedef struct {
 } s4b_curves_out;
 int S4B_FN(predict_curves)(s4b_sampler* s, const s4b_curves_in* in, s4b_curves_out* out);
 
+/* extension (R: bayestestR::describe_posterior / HDInterval::hdi applied to every row of extract(fit) or of samples.icate, formed on the device): the
+ * PER-ROW DESCRIPTION of the posterior — the highest-density interval, the draws above and below thresholds (from which the probability of direction,
+ * the probability of exceeding a cost and the ROPE share follow), the median and the median absolute deviation.  Every output is a function of ONE
+ * thing, the row's draws in sorted order.  For row i let x(0) <= ... <= x(S-1) be its S pooled values in ascending order: x = v(z_1) (n_arms 1:
+ * predict_quantiles' value) or v(z_1) - v(z_0) (n_arms 2: predict_contrast's d), over the draws of `s` and its peers pooled as predict_quantiles pools
+ * them.  The order is that of the usual monotone map of a double's bits to an unsigned integer: -0.0 stands before +0.0.  The values are finite.
+ *   quantiles[q, i]     R's type 7 as predict_quantiles forms it, prob-major: the bits are predict_quantiles' (n_arms 1) / predict_contrast's (n_arms 2)
+ *   median[i]           type 7 at 0.5: x((S-1)/2) for odd S, x(S/2-1) + 0.5 (x(S/2) - x(S/2-1)) for even S; the bits of quantiles at prob 0.5
+ *   hdi[c, 0 / 1, i], hdi_start[c, i]
+ *                       the host hands down an integer hdi_count[c] = m, 1 <= m <= S.  Among the windows j = 0 .. S - m the width is x(j + m - 1) - x(j),
+ *                       one double subtraction; the smallest width wins, on an exact tie the LOWEST j.  hdi = x(j), x(j + m - 1) at
+ *                       hdi[(2 c + e) * n_test + i], hdi_start = j at hdi_start[c * n_test + i].  This is the shortest interval that holds at least m
+ *                       of the draws.  It is restated here from that definition; it is NOT pinned against HDInterval::hdi or bayestestR::hdi (no R in
+ *                       the test environment), which differ from it and from each other by one point of the window, only against the numpy model of
+ *                       tests/describe_cases.py.  The caller chooses m for a mass (the Python binding: ceil(mass S) in exact rational arithmetic).
+ *   n_above[t, i], n_below[t, i]
+ *                       #{k : x(k) > thresholds[t]} and #{k : x(k) < thresholds[t]}, both strict, both in DOUBLE comparison: -0.0 and +0.0 are equal to
+ *                       a threshold of either zero; a draw equal to the threshold counts on neither side.  +-inf allowed, NaN refused.  At [t * n_test + i].
+ *   mad[i]              the type-7 median of |x(k) - median[i]| over the S draws, unscaled (R's mad() multiplies by 1.4826)
+ * Every output may be NULL.  n_hdi <= S4B_DESCRIBE_HDI_MAX, n_thresholds <= S4B_DESCRIBE_THRESHOLDS_MAX, n_probs <= 16, S <= 16384.  The sorted row
+ * alone determines every output: the result does not depend on the chunking, the route, live versus stored samplers, the rows sorted side by side per
+ * workgroup or the order of the peers, hdi_start included.  `arms` is predict_contrast's input with n_weights 0 (there are no row weights: every output
+ * is per row); with n_arms 1 every arm-0 pointer must be NULL.  Refused before anything is launched, info left all zero: n_hdi, n_thresholds or
+ * n_probs outside their range, a hdi_count outside [1, S], a NaN threshold, n_arms outside {1, 2}, an arm-0 pointer with n_arms 1, n_weights != 0,
+ * an output whose count is 0 (quantiles with n_probs 0, hdi or hdi_start with n_hdi 0, n_above or n_below with n_thresholds 0), and whatever
+ * predict_contrast refuses.  The query forms: in = NULL sets num_samples to the kept draws of `s` alone; in given and EVERY output NULL runs all the
+ * checks, sets num_samples to the pooled draws and info to the plan of the call (launches and device bytes 0), and launches nothing.  Per chunk of rows
+ * (C as predict_quantiles chooses it) two launches; device memory: DESIGN.md 5.17 (no term grows with n_test x S beyond a chunk). */
+#define S4B_DESCRIBE_HDI_MAX 8
+#define S4B_DESCRIBE_THRESHOLDS_MAX 32
+typedef struct {
+  s4b_contrast_in arms;           /* rows (n_weights 0), arm 0, probs, peers, scratch_bytes: predict_contrast's meaning */
+  int32_t n_arms;                 /* 1: x = v(z_1), every arm-0 pointer NULL; 2: the contrast */
+  int32_t n_hdi;                  /* 0 .. S4B_DESCRIBE_HDI_MAX */
+  const int32_t* hdi_count;       /* [n_hdi], each in [1, S] */
+  int32_t n_thresholds;           /* 0 .. S4B_DESCRIBE_THRESHOLDS_MAX */
+  const double* thresholds;       /* [n_thresholds], any order, duplicates allowed, no NaN */
+} s4b_describe_in;
+typedef struct {
+  double* quantiles;              /* n_probs x n_test, prob-major */
+  double* median;                 /* n_test */
+  double* hdi;                    /* n_hdi x 2 x n_test */
+  int32_t* hdi_start;             /* n_hdi x n_test */
+  int32_t* n_above; int32_t* n_below;   /* n_thresholds x n_test each */
+  double* mad;                    /* n_test */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did, in s4b_groups_out.info's layout where the entries have a meaning: [0] route of the value kernel (as s4b_contrast_out.info[0]),
+   * [1] rows per chunk, [2] chunks, [3] kernel launches (2 per chunk; 0 for the query), [4] bytes of device memory the call allocated (0 for the query),
+   * [5] pooled draws, [6] (rows sorted side by side per workgroup) << 32 | draws padded to a power of two, [7] bytes of LDS of a sort workgroup */
+  int64_t info[8];
+} s4b_describe_out;
+int S4B_FN(predict_describe)(s4b_sampler* s, const s4b_describe_in* in, s4b_describe_out* out);
+
 /* extension (R: loo::loo() on the rows-times-draws log-likelihood matrix, formed on the device): PSIS-LOO, Pareto-smoothed importance-sampling
  * leave-one-out, per row over the draws of `s` and its peers, pooled as predict_quantiles pools them (the draws of `s`, then the peers' in their order,
  * S in all, S <= 16384).  It follows loo's do_psis_i / psis_smooth_tail / gpdfit (Vehtari, Simpson, Gelman, Yao, Gabry; the fit: Zhang & Stephens

@@ -185,6 +185,16 @@ class CurvesOut(C.Structure):          # s4b_curves_out
                 ("info", C.c_int64 * 8)]
 
 
+class DescribeIn(C.Structure):         # s4b_describe_in
+    _fields_ = [("arms", ContrastIn), ("n_arms", C.c_int32), ("n_hdi", C.c_int32), ("hdi_count", c_int32_p), ("n_thresholds", C.c_int32),
+                ("thresholds", c_double_p)]
+
+
+class DescribeOut(C.Structure):        # s4b_describe_out
+    _fields_ = [("quantiles", c_double_p), ("median", c_double_p), ("hdi", c_double_p), ("hdi_start", c_int32_p), ("n_above", c_int32_p),
+                ("n_below", c_int32_p), ("mad", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
 class PpdOut(C.Structure):             # s4b_ppd_out
     _fields_ = [("quantiles", c_double_p), ("lpd", c_double_p), ("lmean", c_double_p), ("lm2", c_double_p), ("pit", c_double_p),
                 ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
@@ -231,6 +241,10 @@ CHECK_INFO = SPREAD_INFO               # (s4b_check_out.info has s4b_spread_out.
 CURVES_INFO = QUANTILE_INFO[:7] + ("device_bytes", "largest_affected", "total_affected")          # (the last two share info[7], as in PD_INFO)
 CURVES_OUTPUTS = ("mean", "m2", "quantiles", "p_max", "p_min", "range_mean", "range_m2", "range_quantiles")
 CURVES_SCRATCH_MAX = 1 << 30           # S4B_CURVES_SCRATCH_MAX: the curves of 64 rows (8 x 64 x pooled draws x grid points) at most
+DESCRIBE_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes", "draws", "rows_per_sort", "padded_draws", "sort_lds_bytes")
+DESCRIBE_OUTPUTS = ("quantiles", "median", "hdi", "hdi_start", "n_above", "n_below", "mad")
+DESCRIBE_HDI_MAX = 8                   # S4B_DESCRIBE_HDI_MAX: window counts of one s4b_predict_describe call at most
+DESCRIBE_THRESHOLDS_MAX = 32           # S4B_DESCRIBE_THRESHOLDS_MAX: thresholds of one s4b_predict_describe call at most
 PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
 LOO_INFO = QUANTILE_INFO               # (s4b_loo_out.info likewise; rows_per_sort: rows per workgroup of k_loo_rows)
 LOO_OUTPUTS = ("elpd_loo", "pareto_k", "lpd", "ess")
@@ -498,6 +512,7 @@ class Sampler:
             "predict_spread": [vp, C.POINTER(SpreadIn), C.POINTER(SpreadOut)],
             "predict_check": [vp, C.POINTER(CheckIn), C.POINTER(CheckOut)],
             "predict_curves": [vp, C.POINTER(CurvesIn), C.POINTER(CurvesOut)],
+            "predict_describe": [vp, C.POINTER(DescribeIn), C.POINTER(DescribeOut)],
             "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
             "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
             "predict_convergence": [vp, C.POINTER(ConvIn), C.POINTER(ConvOut)],
@@ -1131,6 +1146,65 @@ class Sampler:
         del keep, spare
         return dict(res, draws_pooled=int(out.num_samples), info=dict(self.groups_info))
 
+    def describe_draws(self) -> int:
+        """The kept draws of this sampler, as ``s4b_predict_describe``'s query form without an input reports them."""
+        probe = DescribeOut()
+        self._check(self._f("predict_describe")(self._h, None, C.byref(probe)))
+        return int(probe.num_samples)
+
+    def predict_describe(self, x_test: np.ndarray, x_test0=None, n_arms: int = 1, hdi_count=(), thresholds=(), probs=(), peers=(),
+                         peer_dense_coef=None, peer_ell_coef=None, offset=None, offset0=None, dense=None, dense0=None, dense_coef=None,
+                         ell_index=None, ell_index0=None, ell_value=None, ell_value0=None, ell_coef=None, link: int = 0, weights=None,
+                         outputs=DESCRIBE_OUTPUTS, route="auto", stage_nodes: int = 0, scratch_bytes: int = 0) -> dict:
+        """``s4b_predict_describe``: per row, from its pooled draws in sorted order x(0) <= ... <= x(S-1) — ``n_arms`` 1: ``predict_quantiles``' value,
+        2: ``predict_contrast``'s d, the arms given as there — the ``probs`` type-7 quantiles [probs x rows], the median [rows], for every integer m of
+        ``hdi_count`` (1 <= m <= S, at most DESCRIBE_HDI_MAX) the shortest window of m draws, hdi [counts x 2 x rows] and hdi_start [counts x rows] (the
+        lowest start among the windows of the smallest width), for every threshold (at most DESCRIBE_THRESHOLDS_MAX, no NaN) the draws strictly above
+        and strictly below it, n_above and n_below [thresholds x rows] int32, and the unscaled median absolute deviation mad [rows].  ``outputs``
+        names what is formed, among DESCRIBE_OUTPUTS; an output whose count is 0 (quantiles without probs, hdi and hdi_start without hdi_count,
+        n_above and n_below without thresholds) is left out.  ``outputs`` empty is the query: every check runs, nothing is launched and info holds the
+        plan.  ``weights`` must stay None: there are no row weights.  Returns a dict of the outputs (None where not formed), ``draws`` (pooled) and
+        info: DESCRIBE_INFO."""
+        fn = getattr(self._lib, self._pfx + "predict_describe", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_describe")
+
+        def draws(smp):
+            probe = DescribeOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        unknown = set(outputs) - set(DESCRIBE_OUTPUTS)
+        if unknown:
+            raise ValueError(f"outputs must be among {DESCRIBE_OUTPUTS}, not {sorted(unknown)}")
+        cnt = np.atleast_1d(np.asarray(hdi_count))
+        if cnt.ndim != 1 or (cnt.size and cnt.dtype.kind not in "iu"):
+            raise ValueError("hdi_count must be a vector of integers")
+        if cnt.size and (cnt.min() < -2 ** 31 or cnt.max() >= 2 ** 31):
+            raise ValueError("hdi_count does not fit 32 bits")
+        cnt = _i32(cnt)
+        thr = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+        if thr.ndim != 1:
+            raise ValueError(f"thresholds must be a vector, not shape {thr.shape}")
+        w = None if weights is None else np.asarray(weights, dtype=np.float64)[None, :]
+        arms, keep, rows, _, S, pr = self._contrast_in(draws, x_test, x_test0, probs, peers, peer_dense_coef, peer_ell_coef, offset, offset0, dense, dense0,
+                                                       dense_coef, ell_index, ell_index0, ell_value, ell_value0, ell_coef, link, w, route, stage_nodes,
+                                                       scratch_bytes)
+        n, Q, M, T = max(rows, 1), len(pr), len(cnt), len(thr)
+        shape = dict(quantiles=(Q, n), median=(n,), hdi=(M, 2, n), hdi_start=(M, n), n_above=(T, n), n_below=(T, n), mad=(n,))
+        size = dict(quantiles=Q, hdi=M, hdi_start=M, n_above=T, n_below=T)
+        res = {k: np.zeros(shape[k], dtype=np.int32 if k in ("hdi_start", "n_above", "n_below") else np.float64)
+               if k in outputs and size.get(k, 1) > 0 else None for k in DESCRIBE_OUTPUTS}
+        arg = DescribeIn(arms=arms, n_arms=int(n_arms), n_hdi=M, hdi_count=_ip(cnt) if M else None, n_thresholds=T, thresholds=_dp(thr) if T else None)
+        out = DescribeOut(quantiles=_dp(res["quantiles"]), median=_dp(res["median"]), hdi=_dp(res["hdi"]), hdi_start=_ip(res["hdi_start"]),
+                          n_above=_ip(res["n_above"]), n_below=_ip(res["n_below"]), mad=_dp(res["mad"]))
+        self.describe_info = dict(zip(DESCRIBE_INFO, [0] * 9))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        v = [int(x) for x in out.info]
+        self.describe_info = dict(zip(DESCRIBE_INFO, v[:6] + [v[6] >> 32, v[6] & 0xFFFFFFFF, v[7]]))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep
+        return dict(res, draws=int(out.num_samples), info=dict(self.describe_info))
+
     def projection_draws(self) -> int:
         """The kept draws of this sampler, as ``s4b_predict_projection``'s query form reports them."""
         probe = ProjectionOut()
@@ -1715,6 +1789,8 @@ class StoredSampler:
     check_names = staticmethod(Sampler.check_names)
     predict_check = Sampler.predict_check
     curves_draws = Sampler.curves_draws
+    describe_draws = Sampler.describe_draws
+    predict_describe = Sampler.predict_describe
     predict_curves = Sampler.predict_curves
     predict_ppd = Sampler.predict_ppd
     predict_loo = Sampler.predict_loo

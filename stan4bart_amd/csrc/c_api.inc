@@ -127,6 +127,14 @@ int S4B_FN(predict_curves)(s4b_sampler* s, const s4b_curves_in* in, s4b_curves_o
   s->core.predict_curves(in, out, peers.empty() ? nullptr : peers.data());
   S4B_CATCH
 }
+int S4B_FN(predict_describe)(s4b_sampler* s, const s4b_describe_in* in, s4b_describe_out* out) {
+  S4B_NEED(s, "predict_describe") S4B_TRY
+  s->core.dev().bind();
+  std::vector<const s4b::SamplerCore<S4B_DEV>*> peers;          // (a NULL handle stays NULL: the core refuses it by its position)
+  if (in && out && in->arms.n_peers > 0 && in->arms.peers) for (int x = 0; x < in->arms.n_peers; ++x) peers.push_back(in->arms.peers[x] ? &in->arms.peers[x]->core : nullptr);
+  s->core.predict_describe(in, out, peers.empty() ? nullptr : peers.data());
+  S4B_CATCH
+}
 int S4B_FN(predict_ppd)(s4b_sampler* s, const s4b_ppd_in* in, s4b_ppd_out* out) {
   S4B_NEED(s, "predict_ppd") S4B_TRY
   s->core.dev().bind();

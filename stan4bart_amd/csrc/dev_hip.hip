@@ -1637,6 +1637,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 #include "readout_spread.inc"
 #include "readout_check.inc"
 #include "readout_curves.inc"
+#include "readout_describe.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
 static void use_device(int device) {
@@ -2756,6 +2757,8 @@ class DevHip {
   void predict_check(const CheckCall& c) { check_run(stream_, a_.P, c, launches_); }
   // s4b_predict_curves (readout_curves.inc), likewise
   void predict_curves(const CurvesCall& c) { curves_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_describe (readout_describe.inc), likewise
+  void predict_describe(const DescribeCall& c) { describe_run(stream_, a_.P, c, launches_); }
   // s4b_predict_ppd (dev_ppd.inc), likewise
   void predict_ppd(const PpdCall& c) { ppd_run(stream_, a_.P, c, launches_); }
   // s4b_predict_loo (dev_loo.inc), likewise

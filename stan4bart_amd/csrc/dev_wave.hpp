@@ -69,6 +69,16 @@ __device__ __forceinline__ double wave_min(double v) {
   v = fmin(v, wave_xor<32>(v)); v = fmin(v, wave_xor<16>(v)); v = fmin(v, wave_xor<8>(v)); v = fmin(v, wave_xor<4>(v)); v = fmin(v, wave_xor<2>(v)); v = fmin(v, wave_xor<1>(v));
   return v;
 }
+// the lexicographic minimum of the pairs (v, idx) over the 64 lanes, in every lane: the smallest v, among equal v the lowest idx (no NaN among the v)
+template <int O>
+__device__ __forceinline__ void wave_argmin_step(double& v, int& idx) {
+  const double ov = wave_xor<O>(v);
+  const int oi = wave_xor<O>(idx);
+  if (ov < v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+}
+__device__ __forceinline__ void wave_argmin(double& v, int& idx) {
+  wave_argmin_step<32>(v, idx); wave_argmin_step<16>(v, idx); wave_argmin_step<8>(v, idx); wave_argmin_step<4>(v, idx); wave_argmin_step<2>(v, idx); wave_argmin_step<1>(v, idx);
+}
 __device__ __forceinline__ double wave_max(double v) {
   v = fmax(v, wave_xor<32>(v)); v = fmax(v, wave_xor<16>(v)); v = fmax(v, wave_xor<8>(v)); v = fmax(v, wave_xor<4>(v)); v = fmax(v, wave_xor<2>(v)); v = fmax(v, wave_xor<1>(v));
   return v;

@@ -187,6 +187,18 @@ struct CurvesCall {
   double* rangeMean; double* rangeM2; double* rangeQuantiles;                       // [nT], [nT], [Q x nT]
 };
 
+// does the device layer describe every row's posterior from its sorted draws (s4b_predict_describe)?  As has_predict_curves.
+template <class D, class = void> struct has_predict_describe : std::false_type {};
+template <class D> struct has_predict_describe<D, std::void_t<decltype(&D::predict_describe)>> : std::true_type {};
+// one s4b_predict_describe call as the device layer sees it: the arms as GroupsCall's (the probs inside them), the validated window counts [nMass] and
+// thresholds [nThr], every output NULL where it was not asked for (all NULL: the query, the device layer fills info with the plan and launches nothing)
+struct DescribeCall {
+  ContrastCall arms;
+  int nArms, nMass, nThr; const int32_t* hdiCount; const double* thresholds;
+  double* quantiles; double* median; double* hdi; int32_t* hdiStart;          // [Q x nT], [nT], [nMass x 2 x nT], [nMass x nT]
+  int32_t* nAbove; int32_t* nBelow; double* mad;                              // [nThr x nT], [nThr x nT], [nT]
+};
+
 // does the device layer form the posterior predictive read-out over the pooled kept draws (s4b_predict_ppd)?  As has_predict_quantiles.
 template <class D, class = void> struct has_predict_ppd : std::false_type {};
 template <class D> struct has_predict_ppd<D, std::void_t<decltype(&D::predict_ppd)>> : std::true_type {};
@@ -1148,6 +1160,51 @@ class SamplerCore {
         out->num_samples = S;
         return S;
       } else throw std::invalid_argument("predict_curves: this device layer has no curve kernels (the curves are formed by the HIP library only)");
+    }
+  }
+  // s4b_predict_describe: per row, from its pooled draws in sorted order — one arm: predict_quantiles' value, two arms: predict_contrast's d — the
+  // type-7 quantiles and the median, the shortest window of hdi_count[c] draws, the draws strictly above and strictly below each threshold and the
+  // median absolute deviation.  Everything is validated here, before any launch; with every output NULL the call is the query for the plan.
+  int64_t predict_describe(const s4b_describe_in* in, s4b_describe_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_describe: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in) return own;          // query: the kept draws of this sampler alone
+    {          // (the checks run on every device layer; the layer without the describe kernel refuses what passed them)
+      const std::string who = "predict_describe";
+      const s4b_contrast_in* ar = &in->arms;
+      const s4b_summary_in* rw = &ar->rows;
+      if (rw->n_weights != 0) throw std::invalid_argument(who + ": arms.rows.n_weights must be 0 (every output is per row: there are no row weights), not " + std::to_string(rw->n_weights));
+      contrast_check_in(who, ar, 0);
+      if (in->n_arms != 1 && in->n_arms != 2) throw std::invalid_argument(who + ": n_arms must be 1 (the fitted value) or 2 (the contrast), not " + std::to_string(in->n_arms));
+      if (in->n_arms == 1 && (ar->x_test0 || ar->offset0 || ar->dense0 || ar->ell_index0 || ar->ell_value0))
+        throw std::invalid_argument(who + ": n_arms = 1 takes no arm-0 pointer (x_test0, offset0, dense0, ell_index0, ell_value0 must be NULL)");
+      const int M = in->n_hdi, T = in->n_thresholds;
+      if (M < 0 || M > S4B_DESCRIBE_HDI_MAX) throw std::invalid_argument(who + ": n_hdi must lie in [0, " + std::to_string(S4B_DESCRIBE_HDI_MAX) + "], not " + std::to_string(M));
+      if (M > 0 && !in->hdi_count) throw std::invalid_argument(who + ": NULL hdi_count");
+      if (T < 0 || T > S4B_DESCRIBE_THRESHOLDS_MAX)
+        throw std::invalid_argument(who + ": n_thresholds must lie in [0, " + std::to_string(S4B_DESCRIBE_THRESHOLDS_MAX) + "], not " + std::to_string(T));
+      if (T > 0 && !in->thresholds) throw std::invalid_argument(who + ": NULL thresholds");
+      for (int j = 0; j < T; ++j) if (std::isnan(in->thresholds[j])) throw std::invalid_argument(who + ": threshold " + std::to_string(j) + " is a NaN");
+      if (out->quantiles && ar->n_probs == 0) throw std::invalid_argument(who + ": quantiles given, but n_probs = 0");
+      if ((out->hdi || out->hdi_start) && M == 0) throw std::invalid_argument(who + ": hdi or hdi_start given, but n_hdi = 0");
+      if ((out->n_above || out->n_below) && T == 0) throw std::invalid_argument(who + ": n_above or n_below given, but n_thresholds = 0");
+      DescribeCall g{};
+      ArmsHold hold;
+      const int64_t S = contrast_arms(who, ar, peers, in->n_arms == 2, out->info, g.arms, hold);
+      for (int j = 0; j < M; ++j)
+        if (in->hdi_count[j] < 1 || in->hdi_count[j] > S)
+          throw std::invalid_argument(who + ": hdi_count " + std::to_string(in->hdi_count[j]) + " outside [1, " + std::to_string(S) + "] (the pooled draws)");
+      if constexpr (has_predict_describe<Dev>::value) {
+        g.arms.rows.G = 0; g.arms.rows.weights = nullptr;
+        g.nArms = in->n_arms; g.nMass = M; g.hdiCount = in->hdi_count; g.nThr = T; g.thresholds = in->thresholds;
+        g.quantiles = out->quantiles; g.median = out->median; g.hdi = out->hdi; g.hdiStart = out->hdi_start;
+        g.nAbove = out->n_above; g.nBelow = out->n_below; g.mad = out->mad;
+        dev_.predict_describe(g);
+        out->num_samples = S;
+        return S;
+      } else throw std::invalid_argument("predict_describe: this device layer has no describe kernel (the per-row description is formed by the HIP library only)");
     }
   }
   // s4b_predict_ppd: the posterior predictive distribution of new observations at the rows — type-7 quantiles of y_rep = z + sigma row_scale e — and the

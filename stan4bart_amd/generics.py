@@ -12,11 +12,12 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
+from fractions import Fraction
 from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from .abi import CURVES_OUTPUTS, GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, PROJECTION_COLUMNS_MAX, SPREAD_THRESHOLDS_MAX, Sampler
+from .abi import CURVES_OUTPUTS, DESCRIBE_HDI_MAX, DESCRIBE_THRESHOLDS_MAX, GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, PROJECTION_COLUMNS_MAX, SPREAD_THRESHOLDS_MAX, Sampler
 from .fit import GroupTerm, chain_seeds, hip_sampler_factory, make_sampler_args, make_z_csr, qr_back_transform
 from .rcompat import RRng
 
@@ -770,6 +771,79 @@ class Stan4bartFit:
         if return_draws:
             avg = out["draws"]                                                        # [L, pooled draws], chain after chain
             res["average"] = avg if combine_chains else avg.reshape(L, len(self.samplers), -1).transpose(0, 2, 1)
+        return res
+
+    # ------------------------------------------------------------------ describe_posterior
+    @staticmethod
+    def hdi_draws(ci, draws: int) -> int:
+        """The draws m of the window that holds the mass ``ci`` of ``draws`` pooled draws: ceil(ci x draws) in exact rational arithmetic on the
+        decimal text of ``ci`` (in floating point 0.7 x 10 is 7.000000000000001 and would give 8), clamped to [1, draws]."""
+        c = Fraction(repr(float(ci)))
+        if not 0 < c <= 1:
+            raise ValueError(f"'ci' must hold masses in (0, 1], not {ci!r}")
+        return max(1, min(int(draws), math.ceil(c * int(draws))))
+
+    def describe_posterior(self, x_bart=None, x_bart0=None, X=None, X0=None, groups: Optional[Sequence[GroupTerm]] = None,
+                           groups0: Optional[Sequence[GroupTerm]] = None, offset=None, offset0=None, treatment=None, levels=(1.0, 0.0),
+                           type: str = "ev", ci=(0.95,), thresholds=(), rope=None, probs=(0.025, 0.5, 0.975), mad_constant: float = 1.0,
+                           sample_new_levels: bool = True, seed: Optional[int] = None):
+        """Per-row description of the posterior — what ``bayestestR::describe_posterior`` reports for every row of ``predict``'s matrix or of
+        ``predict_contrast``'s effects — formed on the device without a [rows x draws] matrix, pooled over the chains in ONE call
+        (``s4b_predict_describe``: the first chain's sampler with the others as its peers).  Any arm-0 argument (suffix 0) or ``treatment`` makes
+        it the contrast of two arms, formed as ``predict_contrast`` forms it; otherwise the one arm's expected value as ``predict_quantiles`` forms
+        it.  ``ci``: up to 8 masses in (0, 1]; the highest-density interval of a mass is the shortest window of m = ``hdi_draws(mass, draws)`` of
+        the sorted draws (the lowest on a tie).  ``thresholds``: values whose exceedance is asked for; ``rope`` None or (low, high), the region of
+        practical equivalence.  Every share is formed from the integer counts with one division.  Returns ``median``, ``mad`` (times
+        ``mad_constant``; 1.4826 gives R's ``mad``), ``ci``, ``hdi`` [masses, 2, rows], ``hdi_draws`` [masses], ``hdi_start`` [masses, rows],
+        ``probs`` and ``quantiles`` [Q, rows], ``thresholds`` with ``p_above`` and ``p_below`` [thresholds, rows] (both strict), ``pd`` (the
+        probability of direction, max(P(> 0), P(< 0))), with a ROPE ``rope_share`` (the share of the draws inside [low, high]) and
+        ``rope_share_hdi`` [masses, rows] (the share of the interval's draws inside it), and ``draws``."""
+        if type == "ppd":
+            raise ValueError("describe_posterior does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("describe_posterior requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("describe_posterior needs x_bart, the new rows of the BART predictors")
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or len(pr) > 16 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of at most 16 values in [0, 1], not {probs!r}")
+        masses = [float(c) for c in np.atleast_1d(np.asarray(ci, dtype=np.float64))]
+        if len(masses) > DESCRIBE_HDI_MAX:
+            raise ValueError(f"'ci' holds {len(masses)} masses: at most {DESCRIBE_HDI_MAX} per call")
+        thr = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        if thr.ndim != 1 or np.any(np.isnan(thr)):
+            raise ValueError(f"'thresholds' must be a vector without NaN, not {thresholds!r}")
+        if rope is not None:
+            rope = tuple(float(v) for v in rope)
+            if len(rope) != 2 or not rope[0] <= rope[1]:
+                raise ValueError(f"'rope' must be None or (low, high) with low <= high, not {rope!r}")
+        T = len(thr)
+        internal = np.r_[thr, 0.0, rope if rope is not None else ()]          # the call's thresholds, then 0 and the ends of the ROPE
+        if len(internal) > DESCRIBE_THRESHOLDS_MAX:
+            raise ValueError(f"'thresholds' holds {T} values: at most {DESCRIBE_THRESHOLDS_MAX - (3 if rope is not None else 1)} per call beside the binding's own")
+        two = treatment is not None or any(a is not None for a in (x_bart0, X0, groups0, offset0))
+        x_bart, x_bart0, kw, peer_kw = self._contrast_arms(x_bart, x_bart0, X, X0, groups, groups0, offset, offset0, treatment, levels, type,
+                                                           sample_new_levels, seed)
+        first = self.samplers[0]
+        S = first.describe_draws() + sum(p.describe_draws() for p in peer_kw["peers"])
+        m = np.array([self.hdi_draws(c, S) for c in masses], dtype=np.int32)
+        r = first.predict_describe(x_bart, x_bart0, n_arms=2 if two else 1, hdi_count=m, thresholds=internal, probs=pr, **peer_kw, **kw)
+        na, nb = r["n_above"].astype(np.int64), r["n_below"].astype(np.int64)
+        res = {"median": r["median"], "mad": r["mad"] * float(mad_constant), "ci": np.asarray(masses), "hdi": r["hdi"], "hdi_draws": m.astype(np.int64),
+               "hdi_start": r["hdi_start"], "probs": pr, "quantiles": r["quantiles"], "thresholds": thr, "p_above": na[:T] / S, "p_below": nb[:T] / S,
+               "pd": np.maximum(na[T], nb[T]) / S, "draws": S}
+        if rope is not None:
+            first_in, end_in = nb[T + 1], S - na[T + 2]                      # the sorted draws [first_in, end_in) lie in [low, high]
+            res["rope"] = rope
+            res["rope_share"] = (S - nb[T + 1] - na[T + 2]) / S
+            if len(m):
+                start = r["hdi_start"].astype(np.int64)
+                overlap = np.minimum(start + m[:, None], end_in[None, :]) - np.maximum(start, first_in[None, :])
+                res["rope_share_hdi"] = np.maximum(overlap, 0) / m[:, None].astype(np.int64)
+            else:
+                res["rope_share_hdi"] = np.zeros((0, len(na[T])))
         return res
 
     # ------------------------------------------------------------------ predict_projection
