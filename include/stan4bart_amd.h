@@ -803,6 +803,59 @@ typedef struct {
 } s4b_describe_out;
 int S4B_FN(predict_describe)(s4b_sampler* s, const s4b_describe_in* in, s4b_describe_out* out);
 
+/* extension (R: apply(samples.icate, 2, quantile) and the classification analysis of the sorted effects of Chernozhukov, Fernandez-Val and Luo, formed
+ * on the device): ORDER STATISTICS ACROSS THE ROWS within every pooled draw — the distribution of the individual values over the units, with a
+ * posterior band — and for every row how often it lies beyond a per-draw order statistic (membership of the most and least affected group).
+ * Rows i < n = n_test; pooled draws k < S, over the draws of `s` and its peers pooled as predict_quantiles pools them, S <= 16384.
+ * x(i,k) = v(z_1) (n_arms 1: predict_quantiles' value, k_predict_values' v) or v(z_1) - v(z_0) (n_arms 2: predict_contrast's d).  The values are
+ * finite.  There are no row weights: n_weights must be 0.  For draw k let y_k(0) <= ... <= y_k(n-1) be the column x(., k) in the order of the usual
+ * monotone map of a double's bits to an unsigned 64-bit integer, under which -0.0 stands before +0.0.
+ *   sorted[j, k]        for row_probs[j], j < n_row_probs <= S4B_SORTED_PROBS_MAX, each in [0, 1]: R's type 7 ACROSS THE ROWS.  h = p (n - 1),
+ *                       lo = floor(h), hi = min(lo + 1, n - 1), g = h - lo, formed on the host in double exactly as predict_quantiles forms them over
+ *                       the draws; y(lo) when g = 0, else y(lo) + g (y(hi) - y(lo)) (the product and the sum may contract to one fused multiply-add).
+ *   cut[c, k]           for cut_rank[c], c < n_cuts <= S4B_SORTED_CUTS_MAX, integers in [0, n - 1] in any order, duplicates allowed:
+ *                       y_k(cut_rank[c]), the order statistic itself, bit for bit.
+ *   D                   the matrix [(n_row_probs + n_cuts) x S], statistic-major: the sorted rows, then the cut rows.  Returned as `draws`;
+ *                       mean[m], m2[m] (the sum of squared deviations) and quantiles[q, m] at [q * (n_row_probs + n_cuts) + m] for arms.probs are
+ *                       formed over the draws as predict_spread forms them over its matrix.
+ *   n_above[c, i], n_below[c, i]
+ *                       #{k : x(i,k) > cut[c,k]} and #{k : x(i,k) < cut[c,k]}, int32 at [c * n_test + i], both strict, both in DOUBLE comparison: a
+ *                       value equal to the cut, or a zero of either sign against a zero cut, counts on neither side.
+ * Every output may be NULL.  The result depends on nothing but the multisets of the columns: two calls, both routes, live and stored samplers and any
+ * scratch_bytes (which only sets how many draws are held at once) return the same bits.  Another order of the peers permutes the columns of D and
+ * changes nothing else: n_above, n_below and quantiles are the same bits, mean and m2 add the same numbers in another order.  `arms` is predict_contrast's input;
+ * with n_arms 1 every arm-0 pointer must be NULL.  arms.scratch_bytes limits the values held at once, 8 n_test x (draws of a block): a block is a
+ * multiple of 8 draws, at least 8 (64 n_test bytes where the limit is below that), at most 1024, by default what 64 MiB hold.
+ * Refused before anything is launched, info left all zero: n_row_probs or n_cuts outside their range, a row prob outside [0, 1] or NaN, a cut_rank
+ * outside [0, n_test - 1], n_arms outside {1, 2}, an arm-0 pointer with n_arms 1, n_weights != 0, n_test >= 2^31, an output whose count is 0 (mean,
+ * m2 or draws with n_row_probs + n_cuts = 0, quantiles with that or with n_probs = 0, n_above or n_below with n_cuts = 0), and whatever
+ * predict_contrast refuses.  The query forms: in = NULL sets num_samples to the kept draws of `s` alone; in given and EVERY output NULL runs all the
+ * checks, sets num_samples to the pooled draws and info to the plan of the call (launches and device bytes 0), and launches nothing.  Per block of
+ * draws the value kernel once, 16 launches of the selection and one of the counts (where there are cuts and an output for them); then one launch for D
+ * and the summary's.  Device memory: DESIGN.md 5.18 (8 n_test x draws of a block, and at most 32 MiB of counting tables). */
+#define S4B_SORTED_PROBS_MAX 12
+#define S4B_SORTED_CUTS_MAX 8
+typedef struct {
+  s4b_contrast_in arms;           /* rows (n_weights 0), arm 0, probs (over the draws), peers, scratch_bytes: predict_contrast's meaning */
+  int32_t n_arms;                 /* 1: x = v(z_1), every arm-0 pointer NULL; 2: the contrast */
+  int32_t n_row_probs;            /* 0 .. S4B_SORTED_PROBS_MAX */
+  const double* row_probs;        /* [n_row_probs], each in [0, 1]: across the rows */
+  int32_t n_cuts;                 /* 0 .. S4B_SORTED_CUTS_MAX */
+  const int32_t* cut_rank;        /* [n_cuts], each in [0, n_test - 1] */
+} s4b_sorted_in;
+typedef struct {
+  double* mean; double* m2;       /* n_row_probs + n_cuts each */
+  double* quantiles;              /* n_probs x (n_row_probs + n_cuts), prob-major */
+  double* draws;                  /* D: (n_row_probs + n_cuts) x num_samples, statistic-major */
+  int32_t* n_above; int32_t* n_below;   /* n_cuts x n_test each */
+  int64_t num_samples;            /* pooled draws S */
+  /* what the call did, in s4b_spread_out.info's layout where the entries have a meaning: [0] route of the value kernel (as s4b_contrast_out.info[0]),
+   * [1] draws per block, [2] blocks, [3] kernel launches (0 for the query), [4] bytes of device memory the call allocated (0 for the query),
+   * [5] pooled draws, [6] targets: the distinct ranks selected per draw, [7] selection passes per block (8) */
+  int64_t info[8];
+} s4b_sorted_out;
+int S4B_FN(predict_sorted)(s4b_sampler* s, const s4b_sorted_in* in, s4b_sorted_out* out);
+
 /* extension (R: loo::loo() on the rows-times-draws log-likelihood matrix, formed on the device): PSIS-LOO, Pareto-smoothed importance-sampling
  * leave-one-out, per row over the draws of `s` and its peers, pooled as predict_quantiles pools them (the draws of `s`, then the peers' in their order,
  * S in all, S <= 16384).  It follows loo's do_psis_i / psis_smooth_tail / gpdfit (Vehtari, Simpson, Gelman, Yao, Gabry; the fit: Zhang & Stephens
@@ -1096,6 +1149,18 @@ int S4B_FN(test_hand_off)(s4b_sampler* s, const double* beta, const double* b, d
  * A shape without that path (K > 16 or q > 4096) and the emulated device layer evaluate in plain doubles: info is all 0.  Refused on a stored sampler. */
 #define S4B_STAN_SUMS_INFO 18
 int S4B_FN(test_stan_sums)(s4b_sampler* s, int32_t mode, const double* beta, const double* b, const int32_t* set_exp, double* sums, int64_t* info);
+
+/* TEST ENTRY (no reference counterpart): the selection and the count kernels of s4b_predict_sorted ALONE, on a caller's matrix values [n x S] row-major
+ * (values[i * S + k], finite), in blocks of block_draws columns read in place — no tree is walked, the sampler only lends its device and stream (a
+ * stored sampler will do).  order_stats[r * S + k] = the ranks[r]-th smallest of column k in the key order (-0.0 before +0.0), bit for bit, for
+ * n_ranks ranks in [0, n - 1] in any order, duplicates allowed; n_above / n_below [c * n + i] count the columns in which values[i, k] lies strictly
+ * above / below the cut_rank[c]-th smallest of column k, in double comparison, for n_cuts <= S4B_SORTED_CUTS_MAX cuts.  Any output may be NULL.
+ * Refused: n < 1 or >= 2^31, S outside [1, 16384], block_draws < 1, min(block_draws, S) > 1024, n_ranks outside [0, 32], n_cuts outside
+ * [0, S4B_SORTED_CUTS_MAX], neither ranks nor cuts, more than 32 DISTINCT ranks among ranks and cut_rank together, a rank outside [0, n - 1], NULL
+ * values or info.  info[8]: [0] draws per counting workgroup, [1] draws per block, [2] blocks, [3] launches (17 per block with counts, 16 without, and
+ * one for order_stats), [4] device bytes, [5] S, [6] distinct ranks, [7] passes (8).  The emulated device layer refuses the call. */
+int S4B_FN(test_sorted_select)(s4b_sampler* s, const double* values, int64_t n, int64_t S, int64_t block_draws, int32_t n_ranks, const int32_t* ranks,
+                               double* order_stats, int32_t n_cuts, const int32_t* cut_rank, int32_t* n_above, int32_t* n_below, int64_t* info);
 
 /* finalizer of the externalptr — src/init.cpp:1152-1165 */
 void S4B_FN(free)(s4b_sampler* s);

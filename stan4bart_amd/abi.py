@@ -8,7 +8,9 @@ suite can drive the CPU oracle (``orc_*``, test infrastructure only) through the
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
+from fractions import Fraction
 from typing import Callable, Optional, Sequence
 
 import numpy as np
@@ -195,6 +197,16 @@ class DescribeOut(C.Structure):        # s4b_describe_out
                 ("n_below", c_int32_p), ("mad", c_double_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
 
 
+class SortedIn(C.Structure):           # s4b_sorted_in
+    _fields_ = [("arms", ContrastIn), ("n_arms", C.c_int32), ("n_row_probs", C.c_int32), ("row_probs", c_double_p), ("n_cuts", C.c_int32),
+                ("cut_rank", c_int32_p)]
+
+
+class SortedOut(C.Structure):          # s4b_sorted_out
+    _fields_ = [("mean", c_double_p), ("m2", c_double_p), ("quantiles", c_double_p), ("draws", c_double_p), ("n_above", c_int32_p),
+                ("n_below", c_int32_p), ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
+
+
 class PpdOut(C.Structure):             # s4b_ppd_out
     _fields_ = [("quantiles", c_double_p), ("lpd", c_double_p), ("lmean", c_double_p), ("lm2", c_double_p), ("pit", c_double_p),
                 ("num_samples", C.c_int64), ("info", C.c_int64 * 8)]
@@ -245,6 +257,10 @@ DESCRIBE_INFO = ("route", "rows_per_chunk", "chunks", "launches", "device_bytes"
 DESCRIBE_OUTPUTS = ("quantiles", "median", "hdi", "hdi_start", "n_above", "n_below", "mad")
 DESCRIBE_HDI_MAX = 8                   # S4B_DESCRIBE_HDI_MAX: window counts of one s4b_predict_describe call at most
 DESCRIBE_THRESHOLDS_MAX = 32           # S4B_DESCRIBE_THRESHOLDS_MAX: thresholds of one s4b_predict_describe call at most
+SORTED_INFO = ("route", "draws_per_block", "blocks", "launches", "device_bytes", "draws", "targets", "passes")
+SORTED_OUTPUTS = ("mean", "m2", "quantiles", "draws", "n_above", "n_below")
+SORTED_PROBS_MAX = 12                  # S4B_SORTED_PROBS_MAX: row probs of one s4b_predict_sorted call at most
+SORTED_CUTS_MAX = 8                    # S4B_SORTED_CUTS_MAX: cut ranks of one s4b_predict_sorted call at most
 PPD_INFO = QUANTILE_INFO               # (s4b_ppd_out.info has s4b_quantile_out.info's layout; rows_per_sort: rows per workgroup of k_ppd_rows)
 LOO_INFO = QUANTILE_INFO               # (s4b_loo_out.info likewise; rows_per_sort: rows per workgroup of k_loo_rows)
 LOO_OUTPUTS = ("elpd_loo", "pareto_k", "lpd", "ess")
@@ -284,6 +300,24 @@ def _f64(a, order="F") -> np.ndarray:
 
 def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
+
+
+def ceil_fraction(fraction, count: int):
+    """(the exact fraction, ceil(fraction x count)) in rational arithmetic on the decimal text of ``fraction``: in floating point 0.07 x 100 is
+    7.000000000000001 and would give 8.  Shared by ``Stan4bartFit.hdi_draws`` and ``fraction_count``."""
+    f = Fraction(repr(float(fraction)))
+    return f, math.ceil(f * int(count))
+
+
+def fraction_count(fraction, count: int) -> int:
+    """The members m = ceil(fraction x count) of the top or bottom group of ``count`` rows for ``predict_sorted``, by ``ceil_fraction``: it needs
+    0 < fraction < 1 and m < count."""
+    f, m = ceil_fraction(fraction, count)
+    if not 0 < f < 1:
+        raise ValueError(f"a fraction of the rows must lie in (0, 1), not {fraction!r}")
+    if not m < int(count):
+        raise ValueError(f"the fraction {fraction!r} of {count} rows is all of them ({m}): the group must leave a row outside")
+    return m
 
 
 LATENT_MODES = {"exact": 0, "parallel": 1}      # bart_args latents -> s4b_set_latent_mode
@@ -513,11 +547,13 @@ class Sampler:
             "predict_check": [vp, C.POINTER(CheckIn), C.POINTER(CheckOut)],
             "predict_curves": [vp, C.POINTER(CurvesIn), C.POINTER(CurvesOut)],
             "predict_describe": [vp, C.POINTER(DescribeIn), C.POINTER(DescribeOut)],
+            "predict_sorted": [vp, C.POINTER(SortedIn), C.POINTER(SortedOut)],
             "predict_ppd": [vp, C.POINTER(PpdIn), C.POINTER(PpdOut)],
             "predict_loo": [vp, C.POINTER(LooIn), C.POINTER(LooOut)],
             "predict_convergence": [vp, C.POINTER(ConvIn), C.POINTER(ConvOut)],
             "set_latent_mode": [vp, i32], "get_latent_mode": [vp, ip], "test_draw_latents": [vp], "test_hand_off": [vp, dp, dp, C.c_double, i32],
             "test_stan_sums": [vp, i32, dp, dp, ip, dp, C.POINTER(i64)],
+            "test_sorted_select": [vp, dp, i64, i64, i64, i32, ip, dp, i32, ip, ip, ip, C.POINTER(i64)],
         }
         for name, argtypes in sig.items():
             fn = getattr(self._lib, self._pfx + name, None)
@@ -1205,6 +1241,97 @@ class Sampler:
         del keep
         return dict(res, draws=int(out.num_samples), info=dict(self.describe_info))
 
+    def sorted_draws(self) -> int:
+        """The kept draws of this sampler, as ``s4b_predict_sorted``'s query form without an input reports them."""
+        probe = SortedOut()
+        self._check(self._f("predict_sorted")(self._h, None, C.byref(probe)))
+        return int(probe.num_samples)
+
+    def predict_sorted(self, x_test: np.ndarray, x_test0=None, n_arms: int = 1, row_probs=(), top=(), bottom=(), cut_rank=(), probs=(), peers=(),
+                       peer_dense_coef=None, peer_ell_coef=None, offset=None, offset0=None, dense=None, dense0=None, dense_coef=None,
+                       ell_index=None, ell_index0=None, ell_value=None, ell_value0=None, ell_coef=None, link: int = 0, weights=None,
+                       outputs=SORTED_OUTPUTS, route="auto", stage_nodes: int = 0, scratch_bytes: int = 0) -> dict:
+        """``s4b_predict_sorted``: per pooled draw the order statistics of the rows' values ACROSS THE ROWS — ``n_arms`` 1: ``predict_quantiles``'
+        value, 2: ``predict_contrast``'s d, the arms given as there.  ``row_probs`` (at most SORTED_PROBS_MAX, in [0, 1]): the type-7 quantiles
+        across the rows, the rows ``sorted`` of the statistics matrix.  The cuts (at most SORTED_CUTS_MAX together), the rows ``cut`` behind them:
+        for each fraction f of ``top``, 0 < f < 1, with m = ``fraction_count(f, rows)`` < rows, the rank rows - m - 1 — the m rows strictly above it
+        are the top group of the draw; for each fraction of ``bottom`` the rank m — the m rows strictly below it are the bottom group; then the
+        ranks of ``cut_rank`` as they are.  Over the draws the mean, m2 and the ``probs`` quantiles of every statistic; per cut and row the int32
+        counts ``n_above`` and ``n_below`` of the draws in which the row lies strictly above / below the cut, and from them ``p_top``
+        [top x rows] = n_above / draws and ``p_bottom`` [bottom x rows] = n_below / draws.  ``outputs`` names what is formed, among SORTED_OUTPUTS;
+        an output whose count is 0 is left out; ``outputs`` empty is the query: every check runs, nothing is launched and info holds the plan.
+        ``weights`` must stay None: ranks are unweighted.  Returns mean, m2 [Qr + J], quantiles [Q x (Qr + J)], draws [(Qr + J) x pooled draws]
+        (None where not formed), n_above, n_below, p_top, p_bottom, cut_rank (all J ranks), top_count, bottom_count, row_probs, ``draws_pooled``
+        and info: SORTED_INFO."""
+        fn = getattr(self._lib, self._pfx + "predict_sorted", None)
+        if fn is None:
+            raise RuntimeError(f"this library ({self._pfx}*) has no predict_sorted")
+
+        def draws(smp):
+            probe = SortedOut()
+            smp._check(fn(smp._h, None, C.byref(probe)))
+            return int(probe.num_samples)
+        unknown = set(outputs) - set(SORTED_OUTPUTS)
+        if unknown:
+            raise ValueError(f"outputs must be among {SORTED_OUTPUTS}, not {sorted(unknown)}")
+        rp = np.ascontiguousarray(np.atleast_1d(np.asarray(row_probs, dtype=np.float64)))
+        if rp.ndim != 1:
+            raise ValueError(f"row_probs must be a vector, not shape {rp.shape}")
+        n_rows = int(np.shape(x_test)[0])
+        tc = [fraction_count(f, n_rows) for f in np.atleast_1d(np.asarray(top, dtype=np.float64))]
+        bc = [fraction_count(f, n_rows) for f in np.atleast_1d(np.asarray(bottom, dtype=np.float64))]
+        extra = np.atleast_1d(np.asarray(cut_rank))
+        if extra.ndim != 1 or (extra.size and extra.dtype.kind not in "iu"):
+            raise ValueError("cut_rank must be a vector of integers")
+        if extra.size and (extra.min() < -2 ** 31 or extra.max() >= 2 ** 31):
+            raise ValueError("cut_rank does not fit 32 bits")
+        cuts = _i32(np.r_[[n_rows - m - 1 for m in tc], bc, extra].astype(np.int64))
+        w = None if weights is None else np.asarray(weights, dtype=np.float64)[None, :]
+        arms, keep, rows, _, S, pr = self._contrast_in(draws, x_test, x_test0, probs, peers, peer_dense_coef, peer_ell_coef, offset, offset0, dense, dense0,
+                                                       dense_coef, ell_index, ell_index0, ell_value, ell_value0, ell_coef, link, w, route, stage_nodes,
+                                                       scratch_bytes)
+        n, Q, Qr, J = max(rows, 1), len(pr), len(rp), len(cuts)
+        L = min(Qr, SORTED_PROBS_MAX) + min(J, SORTED_CUTS_MAX)          # (more are refused by the library: no array is sized by them)
+        Jc = min(J, SORTED_CUTS_MAX)
+        shape = dict(mean=(L,), m2=(L,), quantiles=(Q, L), draws=(L, S), n_above=(Jc, n), n_below=(Jc, n))
+        size = dict(mean=L, m2=L, quantiles=Q * L, draws=L, n_above=Jc, n_below=Jc)
+        res = {k: np.zeros(shape[k], dtype=np.int32 if k in ("n_above", "n_below") else np.float64) if k in outputs and size[k] > 0 else None
+               for k in SORTED_OUTPUTS}
+        arg = SortedIn(arms=arms, n_arms=int(n_arms), n_row_probs=Qr, row_probs=_dp(rp) if Qr else None, n_cuts=J, cut_rank=_ip(cuts) if J else None)
+        out = SortedOut(mean=_dp(res["mean"]), m2=_dp(res["m2"]), quantiles=_dp(res["quantiles"]), draws=_dp(res["draws"]),
+                        n_above=_ip(res["n_above"]), n_below=_ip(res["n_below"]))
+        self.sorted_info = dict(zip(SORTED_INFO, [0] * 8))
+        rc = fn(self._h, C.byref(arg), C.byref(out))
+        self.sorted_info = dict(zip(SORTED_INFO, (int(v) for v in out.info)))          # (all zero after a refusal: nothing was launched)
+        self._check(rc)
+        del keep
+        Sp = int(out.num_samples)
+        nt, nb = len(tc), len(bc)
+        p_top = res["n_above"][:nt].astype(np.int64) / Sp if res["n_above"] is not None else None
+        p_bottom = res["n_below"][nt:nt + nb].astype(np.int64) / Sp if res["n_below"] is not None else None
+        return dict(res, p_top=p_top, p_bottom=p_bottom, cut_rank=cuts.astype(np.int64), top_count=np.asarray(tc, dtype=np.int64),
+                    bottom_count=np.asarray(bc, dtype=np.int64), row_probs=rp, draws_pooled=Sp, info=dict(self.sorted_info))
+
+    def test_sorted_select(self, values, block_draws: int, ranks=(), cut_rank=(), outputs=("order_stats", "n_above", "n_below")) -> dict:
+        """``s4b_test_sorted_select``: the selection and the count kernels of ``predict_sorted`` alone on ``values`` [n x S] in blocks of
+        ``block_draws`` columns.  Returns order_stats [ranks x S], n_above, n_below [cuts x n] (None where not asked for or empty) and info."""
+        fn = self._f("test_sorted_select")
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.float64))
+        if v.ndim != 2:
+            raise ValueError(f"values must be [n x S], not shape {v.shape}")
+        n, S = v.shape
+        rk, ct = _i32(np.atleast_1d(np.asarray(ranks, dtype=np.int64))), _i32(np.atleast_1d(np.asarray(cut_rank, dtype=np.int64)))
+        R, J = len(rk), len(ct)
+        ostat = np.zeros((R, S)) if "order_stats" in outputs and R else None
+        above = np.zeros((J, n), dtype=np.int32) if "n_above" in outputs and J else None
+        below = np.zeros((J, n), dtype=np.int32) if "n_below" in outputs and J else None
+        info = np.zeros(8, dtype=np.int64)
+        self._check(fn(self._h, _dp(v), n, S, int(block_draws), R, _ip(rk) if R else None, _dp(ostat), J, _ip(ct) if J else None, _ip(above), _ip(below),
+                       info.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(order_stats=ostat, n_above=above, n_below=below,
+                    info=dict(zip(("draws_per_workgroup", "draws_per_block", "blocks", "launches", "device_bytes", "draws", "targets", "passes"),
+                                  (int(x) for x in info))))
+
     def projection_draws(self) -> int:
         """The kept draws of this sampler, as ``s4b_predict_projection``'s query form reports them."""
         probe = ProjectionOut()
@@ -1791,6 +1918,9 @@ class StoredSampler:
     curves_draws = Sampler.curves_draws
     describe_draws = Sampler.describe_draws
     predict_describe = Sampler.predict_describe
+    sorted_draws = Sampler.sorted_draws
+    predict_sorted = Sampler.predict_sorted
+    test_sorted_select = Sampler.test_sorted_select
     predict_curves = Sampler.predict_curves
     predict_ppd = Sampler.predict_ppd
     predict_loo = Sampler.predict_loo

@@ -135,6 +135,14 @@ int S4B_FN(predict_describe)(s4b_sampler* s, const s4b_describe_in* in, s4b_desc
   s->core.predict_describe(in, out, peers.empty() ? nullptr : peers.data());
   S4B_CATCH
 }
+int S4B_FN(predict_sorted)(s4b_sampler* s, const s4b_sorted_in* in, s4b_sorted_out* out) {
+  S4B_NEED(s, "predict_sorted") S4B_TRY
+  s->core.dev().bind();
+  std::vector<const s4b::SamplerCore<S4B_DEV>*> peers;          // (a NULL handle stays NULL: the core refuses it by its position)
+  if (in && out && in->arms.n_peers > 0 && in->arms.peers) for (int x = 0; x < in->arms.n_peers; ++x) peers.push_back(in->arms.peers[x] ? &in->arms.peers[x]->core : nullptr);
+  s->core.predict_sorted(in, out, peers.empty() ? nullptr : peers.data());
+  S4B_CATCH
+}
 int S4B_FN(predict_ppd)(s4b_sampler* s, const s4b_ppd_in* in, s4b_ppd_out* out) {
   S4B_NEED(s, "predict_ppd") S4B_TRY
   s->core.dev().bind();
@@ -192,6 +200,11 @@ int S4B_FN(test_hand_off)(s4b_sampler* s, const double* beta, const double* b, d
 }
 int S4B_FN(test_stan_sums)(s4b_sampler* s, int32_t mode, const double* beta, const double* b, const int32_t* set_exp, double* sums, int64_t* info) {
   S4B_NEED(s, "test_stan_sums") S4B_TRY s->core.dev().bind(); s->core.test_stan_sums(mode, beta, b, set_exp, sums, info); S4B_CATCH
+}
+int S4B_FN(test_sorted_select)(s4b_sampler* s, const double* values, int64_t n, int64_t S, int64_t block_draws, int32_t n_ranks, const int32_t* ranks,
+                               double* order_stats, int32_t n_cuts, const int32_t* cut_rank, int32_t* n_above, int32_t* n_below, int64_t* info) {
+  S4B_NEED(s, "test_sorted_select") S4B_TRY s->core.dev().bind();
+  s->core.test_sorted_select(values, n, S, block_draws, n_ranks, ranks, order_stats, n_cuts, cut_rank, n_above, n_below, info); S4B_CATCH
 }
 int S4B_FN(get_sweep_busy)(s4b_sampler* s, int64_t* out) { S4B_NEED(s, "get_sweep_busy") S4B_TRY if (!out) throw std::invalid_argument("get_sweep_busy: NULL output pointer"); *out = s->core.dev().sweep_busy(); S4B_CATCH }
 int S4B_FN(get_counters)(s4b_sampler* s, int64_t out[3]) { S4B_NEED(s, "get_counters") S4B_TRY s->core.dev().bind(); s->core.counters(out); S4B_CATCH }

@@ -1638,6 +1638,7 @@ __global__ __launch_bounds__(BLOCK) void k_predict(const uint16_t* xb, int64_t n
 #include "readout_check.inc"
 #include "readout_curves.inc"
 #include "readout_describe.inc"
+#include "readout_sorted.inc"
 
 // every entry that takes a device ordinal: checks it and makes it the calling thread's device
 static void use_device(int device) {
@@ -2759,6 +2760,10 @@ class DevHip {
   void predict_curves(const CurvesCall& c) { curves_run(stream_, a_.P, c, launches_); }
   // s4b_predict_describe (readout_describe.inc), likewise
   void predict_describe(const DescribeCall& c) { describe_run(stream_, a_.P, c, launches_); }
+  // s4b_predict_sorted (readout_sorted.inc), likewise
+  void predict_sorted(const SortedCall& c) { sorted_run(stream_, a_.P, c, launches_); }
+  // TEST ENTRY (s4b_test_sorted_select): readout_sorted.inc's selection and count kernels alone, on the sampler's stream
+  void test_sorted_select(const SortedSelectCall& c) { sorted_select_test(stream_, c, launches_); }
   // s4b_predict_ppd (dev_ppd.inc), likewise
   void predict_ppd(const PpdCall& c) { ppd_run(stream_, a_.P, c, launches_); }
   // s4b_predict_loo (dev_loo.inc), likewise

@@ -199,6 +199,29 @@ struct DescribeCall {
   int32_t* nAbove; int32_t* nBelow; double* mad;                              // [nThr x nT], [nThr x nT], [nT]
 };
 
+// does the device layer select order statistics across the rows per pooled draw (s4b_predict_sorted)?  As has_predict_describe.
+template <class D, class = void> struct has_predict_sorted : std::false_type {};
+template <class D> struct has_predict_sorted<D, std::void_t<decltype(&D::predict_sorted)>> : std::true_type {};
+// one s4b_predict_sorted call as the device layer sees it: the arms as GroupsCall's (the probs over the draws inside them), the validated row probs
+// [Qr] and cut ranks [J], every output NULL where it was not asked for (all NULL: the query, the device layer fills info with the plan and launches
+// nothing)
+struct SortedCall {
+  ContrastCall arms;
+  int nArms, Qr, J; const double* rowProbs; const int32_t* cutRank;
+  double* mean; double* m2; double* quantiles; double* draws;          // [Qr + J], [Qr + J], [Q x (Qr + J)], [(Qr + J) x S]
+  int32_t* nAbove; int32_t* nBelow;                                    // [J x nT] each
+};
+// does the device layer run the selection and count kernels alone (s4b_test_sorted_select)?  Refused where it is missing.
+template <class D, class = void> struct has_test_sorted_select : std::false_type {};
+template <class D> struct has_test_sorted_select<D, std::void_t<decltype(&D::test_sorted_select)>> : std::true_type {};
+// one s4b_test_sorted_select call, validated: values [n x S] row-major, the ranks and the cuts, every output NULL where it was not asked for
+struct SortedSelectCall {
+  const double* values; int64_t n, S, blockDraws;
+  int nRanks; const int32_t* ranks; double* orderStats;                // [nRanks], [nRanks x S]
+  int nCuts; const int32_t* cutRank; int32_t* nAbove; int32_t* nBelow; // [nCuts], [nCuts x n] each
+  int64_t* info;
+};
+
 // does the device layer form the posterior predictive read-out over the pooled kept draws (s4b_predict_ppd)?  As has_predict_quantiles.
 template <class D, class = void> struct has_predict_ppd : std::false_type {};
 template <class D> struct has_predict_ppd<D, std::void_t<decltype(&D::predict_ppd)>> : std::true_type {};
@@ -1206,6 +1229,80 @@ class SamplerCore {
         return S;
       } else throw std::invalid_argument("predict_describe: this device layer has no describe kernel (the per-row description is formed by the HIP library only)");
     }
+  }
+  // s4b_predict_sorted: per pooled draw the order statistics of the rows' values ACROSS THE ROWS — one arm: predict_quantiles' value, two arms:
+  // predict_contrast's d — as type-7 quantiles at the row probs and as the order statistics at the cut ranks themselves; of those series the mean, m2
+  // and type-7 quantiles over the draws; per row and cut the draws in which the row lies strictly above and strictly below the cut.  Everything is
+  // validated here, before any launch; with every output NULL the call is the query for the plan.
+  int64_t predict_sorted(const s4b_sorted_in* in, s4b_sorted_out* out, const SamplerCore* const* peers) {
+    if (!out) throw std::invalid_argument("predict_sorted: NULL output struct");
+    for (int j = 0; j < 8; ++j) out->info[j] = 0;
+    const int64_t own = (int64_t)keptScale_.size() / 2;
+    out->num_samples = own;
+    if (!in) return own;          // query: the kept draws of this sampler alone
+    {          // (the checks run on every device layer; the layer without the kernels refuses what passed them)
+      const std::string who = "predict_sorted";
+      const s4b_contrast_in* ar = &in->arms;
+      const s4b_summary_in* rw = &ar->rows;
+      if (rw->n_weights != 0) throw std::invalid_argument(who + ": arms.rows.n_weights must be 0 (ranks across the rows are unweighted: there are no row weights), not " + std::to_string(rw->n_weights));
+      contrast_check_in(who, ar, 0);
+      if (rw->n_test >= ((int64_t)1 << 31)) throw std::invalid_argument(who + ": n_test must be below 2^31 (a rank is a 32-bit integer), not " + std::to_string(rw->n_test));
+      if (in->n_arms != 1 && in->n_arms != 2) throw std::invalid_argument(who + ": n_arms must be 1 (the fitted value) or 2 (the contrast), not " + std::to_string(in->n_arms));
+      if (in->n_arms == 1 && (ar->x_test0 || ar->offset0 || ar->dense0 || ar->ell_index0 || ar->ell_value0))
+        throw std::invalid_argument(who + ": n_arms = 1 takes no arm-0 pointer (x_test0, offset0, dense0, ell_index0, ell_value0 must be NULL)");
+      const int Qr = in->n_row_probs, J = in->n_cuts;
+      if (Qr < 0 || Qr > S4B_SORTED_PROBS_MAX)
+        throw std::invalid_argument(who + ": n_row_probs must lie in [0, " + std::to_string(S4B_SORTED_PROBS_MAX) + "], not " + std::to_string(Qr));
+      if (Qr > 0 && !in->row_probs) throw std::invalid_argument(who + ": NULL row_probs");
+      for (int j = 0; j < Qr; ++j)
+        if (!(in->row_probs[j] >= 0.0 && in->row_probs[j] <= 1.0)) throw std::invalid_argument(who + ": row prob " + std::to_string(in->row_probs[j]) + " outside [0, 1]");
+      if (J < 0 || J > S4B_SORTED_CUTS_MAX) throw std::invalid_argument(who + ": n_cuts must lie in [0, " + std::to_string(S4B_SORTED_CUTS_MAX) + "], not " + std::to_string(J));
+      if (J > 0 && !in->cut_rank) throw std::invalid_argument(who + ": NULL cut_rank");
+      for (int j = 0; j < J; ++j)
+        if (in->cut_rank[j] < 0 || in->cut_rank[j] >= rw->n_test)
+          throw std::invalid_argument(who + ": cut_rank " + std::to_string(in->cut_rank[j]) + " outside [0, " + std::to_string(rw->n_test - 1) + "] (the rows)");
+      if ((out->mean || out->m2 || out->draws || out->quantiles) && Qr + J == 0) throw std::invalid_argument(who + ": mean, m2, quantiles or draws given, but n_row_probs + n_cuts = 0");
+      if (out->quantiles && ar->n_probs == 0) throw std::invalid_argument(who + ": quantiles given, but n_probs = 0");
+      if ((out->n_above || out->n_below) && J == 0) throw std::invalid_argument(who + ": n_above or n_below given, but n_cuts = 0");
+      SortedCall g{};
+      ArmsHold hold;
+      const int64_t S = contrast_arms(who, ar, peers, in->n_arms == 2, out->info, g.arms, hold);
+      if constexpr (has_predict_sorted<Dev>::value) {
+        g.arms.rows.G = 0; g.arms.rows.weights = nullptr;
+        g.nArms = in->n_arms; g.Qr = Qr; g.rowProbs = in->row_probs; g.J = J; g.cutRank = in->cut_rank;
+        g.mean = out->mean; g.m2 = out->m2; g.quantiles = out->quantiles; g.draws = out->draws; g.nAbove = out->n_above; g.nBelow = out->n_below;
+        dev_.predict_sorted(g);
+        out->num_samples = S;
+        return S;
+      } else throw std::invalid_argument("predict_sorted: this device layer has no selection kernels (the order statistics across the rows are formed by the HIP library only)");
+    }
+  }
+  // TEST ENTRY (s4b_test_sorted_select): the selection and the count kernels of predict_sorted alone on the caller's matrix; the checks run on every layer
+  void test_sorted_select(const double* values, int64_t n, int64_t S, int64_t blockDraws, int nRanks, const int32_t* ranks, double* orderStats, int nCuts,
+                          const int32_t* cutRank, int32_t* nAbove, int32_t* nBelow, int64_t* info) {
+    const std::string who = "test_sorted_select";
+    if (!values || !info) throw std::invalid_argument(who + ": NULL values or info");
+    for (int j = 0; j < 8; ++j) info[j] = 0;
+    if (n < 1 || n >= ((int64_t)1 << 31)) throw std::invalid_argument(who + ": n must lie in [1, 2^31), not " + std::to_string(n));
+    if (S < 1 || S > 16384) throw std::invalid_argument(who + ": S must lie in [1, 16384], not " + std::to_string(S));
+    if (blockDraws < 1 || std::min(blockDraws, S) > 1024) throw std::invalid_argument(who + ": block_draws must be at least 1 and a block at most 1024 draws, not " + std::to_string(blockDraws));
+    if (nRanks < 0 || nRanks > 32) throw std::invalid_argument(who + ": n_ranks must lie in [0, 32], not " + std::to_string(nRanks));
+    if (nCuts < 0 || nCuts > S4B_SORTED_CUTS_MAX) throw std::invalid_argument(who + ": n_cuts must lie in [0, " + std::to_string(S4B_SORTED_CUTS_MAX) + "], not " + std::to_string(nCuts));
+    if (nRanks + nCuts == 0) throw std::invalid_argument(who + ": neither ranks nor cuts");
+    if ((nRanks > 0 && !ranks) || (nCuts > 0 && !cutRank)) throw std::invalid_argument(who + ": NULL ranks or cut_rank");
+    std::vector<int32_t> all;
+    for (int j = 0; j < nRanks + nCuts; ++j) {
+      const int32_t r = j < nRanks ? ranks[j] : cutRank[j - nRanks];
+      if (r < 0 || r >= n) throw std::invalid_argument(who + ": rank " + std::to_string(r) + " outside [0, " + std::to_string(n - 1) + "]");
+      all.push_back(r);
+    }
+    std::sort(all.begin(), all.end());
+    if (std::unique(all.begin(), all.end()) - all.begin() > 32) throw std::invalid_argument(who + ": more than 32 distinct ranks among ranks and cut_rank");
+    for (size_t x = 0, m = (size_t)n * (size_t)S; x < m; ++x) if (!std::isfinite(values[x])) throw std::invalid_argument(who + ": values holds a value that is not finite");
+    if constexpr (has_test_sorted_select<Dev>::value) {
+      SortedSelectCall c{values, n, S, blockDraws, nRanks, ranks, orderStats, nCuts, cutRank, nAbove, nBelow, info};
+      dev_.test_sorted_select(c);
+    } else throw std::invalid_argument("test_sorted_select: this device layer has no selection kernels");
   }
   // s4b_predict_ppd: the posterior predictive distribution of new observations at the rows — type-7 quantiles of y_rep = z + sigma row_scale e — and the
   // scores of held-out responses y (log predictive density, mean and squared deviations of the pointwise log-likelihood, PIT), per row over the

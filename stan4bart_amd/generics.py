@@ -12,12 +12,12 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from fractions import Fraction
 from typing import Callable, Optional, Sequence
 
 import numpy as np
 
-from .abi import CURVES_OUTPUTS, DESCRIBE_HDI_MAX, DESCRIBE_THRESHOLDS_MAX, GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, PROJECTION_COLUMNS_MAX, SPREAD_THRESHOLDS_MAX, Sampler
+from .abi import (CURVES_OUTPUTS, DESCRIBE_HDI_MAX, DESCRIBE_THRESHOLDS_MAX, GROUPS_LEVEL_BYTES_MAX, GROUPS_STATISTICS, PD_GRID_MAX, PROJECTION_COLUMNS_MAX,
+                  SORTED_CUTS_MAX, SORTED_PROBS_MAX, SPREAD_THRESHOLDS_MAX, Sampler, ceil_fraction, fraction_count)
 from .fit import GroupTerm, chain_seeds, hip_sampler_factory, make_sampler_args, make_z_csr, qr_back_transform
 from .rcompat import RRng
 
@@ -778,10 +778,10 @@ class Stan4bartFit:
     def hdi_draws(ci, draws: int) -> int:
         """The draws m of the window that holds the mass ``ci`` of ``draws`` pooled draws: ceil(ci x draws) in exact rational arithmetic on the
         decimal text of ``ci`` (in floating point 0.7 x 10 is 7.000000000000001 and would give 8), clamped to [1, draws]."""
-        c = Fraction(repr(float(ci)))
+        c, m = ceil_fraction(ci, draws)
         if not 0 < c <= 1:
             raise ValueError(f"'ci' must hold masses in (0, 1], not {ci!r}")
-        return max(1, min(int(draws), math.ceil(c * int(draws))))
+        return max(1, min(int(draws), m))
 
     def describe_posterior(self, x_bart=None, x_bart0=None, X=None, X0=None, groups: Optional[Sequence[GroupTerm]] = None,
                            groups0: Optional[Sequence[GroupTerm]] = None, offset=None, offset0=None, treatment=None, levels=(1.0, 0.0),
@@ -845,6 +845,63 @@ class Stan4bartFit:
             else:
                 res["rope_share_hdi"] = np.zeros((0, len(na[T])))
         return res
+
+    # ------------------------------------------------------------------ predict_sorted
+    def predict_sorted(self, x_bart=None, x_bart0=None, X=None, X0=None, groups: Optional[Sequence[GroupTerm]] = None,
+                       groups0: Optional[Sequence[GroupTerm]] = None, offset=None, offset0=None, treatment=None, levels=(1.0, 0.0),
+                       row_probs=(0.1, 0.25, 0.5, 0.75, 0.9), top=(0.1,), bottom=(0.1,), probs=(0.025, 0.5, 0.975), return_draws: bool = False,
+                       type: str = "ev", sample_new_levels: bool = True, seed: Optional[int] = None):
+        """Sorted effects: the distribution of the rows' values ACROSS THE ROWS within a posterior draw — its quantiles at ``row_probs``, each with
+        a posterior band — and for every row the posterior probability of belonging to the most and the least affected group.  Any arm-0 argument
+        (suffix 0) or ``treatment`` makes the values the contrast of two arms as ``predict_contrast`` forms it, otherwise the one arm's expected
+        value as ``predict_quantiles`` forms it.  On the device without a [rows x draws] matrix and in ONE pooled call (``s4b_predict_sorted``: the
+        first chain's sampler with the others as its peers).  ``top`` / ``bottom``: fractions f in (0, 1); the group of a draw is its
+        m = ceil(f x rows) rows with the largest / smallest values (exact rational arithmetic on the decimal text of f, m < rows; with ties at
+        the boundary fewer rows lie strictly beyond it).  Returns ``row_probs`` and ``sorted``, ``top`` / ``bottom`` (the fractions),
+        ``top_count`` / ``bottom_count`` (m), ``cut_rank`` and ``cut`` (the per-draw boundary values: a row is in the top group of a draw when it
+        lies strictly above the cut), each of ``sorted`` and ``cut`` a dict of ``mean``, ``sd`` (over the draws, ddof 1), ``quantiles`` [Q,
+        statistics] and with ``return_draws`` ``draws`` [statistics, draws] chain after chain; ``p_top`` [top, rows] and ``p_bottom``
+        [bottom, rows]; the raw int32 counts ``n_above`` and ``n_below`` [cuts, rows]; ``probs``, ``draws`` (the pooled count) and ``info``."""
+        if type == "ppd":
+            raise ValueError("predict_sorted does not form 'ppd': its noise is drawn per element of the draws matrix (use predict)")
+        if type not in ("ev", "indiv.bart"):
+            raise ValueError("'type' must be one of ev, indiv.bart (indiv.fixef and indiv.ranef need no trees: use predict)")
+        if not self.samplers:
+            raise ValueError("predict_sorted requires 'bart_args' to contain 'keepTrees' as True")
+        if x_bart is None:
+            raise ValueError("predict_sorted needs x_bart, the new rows of the BART predictors")
+        pr = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if pr.ndim != 1 or len(pr) > 16 or not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError(f"'probs' must be a vector of at most 16 values in [0, 1], not {probs!r}")
+        rp = np.atleast_1d(np.asarray(row_probs, dtype=np.float64))
+        if rp.ndim != 1 or len(rp) > SORTED_PROBS_MAX or not np.all((rp >= 0.0) & (rp <= 1.0)):
+            raise ValueError(f"'row_probs' must be a vector of at most {SORTED_PROBS_MAX} values in [0, 1], not {row_probs!r}")
+        tf = [float(f) for f in np.atleast_1d(np.asarray(top, dtype=np.float64))]
+        bf = [float(f) for f in np.atleast_1d(np.asarray(bottom, dtype=np.float64))]
+        if len(tf) + len(bf) > SORTED_CUTS_MAX:
+            raise ValueError(f"'top' and 'bottom' hold {len(tf) + len(bf)} fractions together: at most {SORTED_CUTS_MAX} per call")
+        rows = np.shape(x_bart)[0]
+        for f in tf + bf:
+            fraction_count(f, rows)          # (refused here, before the arms are formed)
+        two = treatment is not None or any(a is not None for a in (x_bart0, X0, groups0, offset0))
+        x_bart, x_bart0, kw, peer_kw = self._contrast_arms(x_bart, x_bart0, X, X0, groups, groups0, offset, offset0, treatment, levels, type,
+                                                           sample_new_levels, seed)
+        r = self.samplers[0].predict_sorted(x_bart, x_bart0, n_arms=2 if two else 1, row_probs=rp, top=tf, bottom=bf, probs=pr, **peer_kw, **kw)
+        S, Qr = r["draws_pooled"], len(rp)
+        L = Qr + len(tf) + len(bf)
+
+        def part(rows_of):
+            if L == 0:
+                return None
+            m2 = r["m2"][rows_of]
+            out = {"mean": r["mean"][rows_of], "sd": np.sqrt(m2 / (S - 1)) if S > 1 else np.full(len(m2), np.nan),
+                   "quantiles": r["quantiles"][:, rows_of] if r["quantiles"] is not None else np.zeros((0, len(m2)))}
+            if return_draws:
+                out["draws"] = r["draws"][rows_of]
+            return out
+        return {"row_probs": rp, "sorted": part(slice(0, Qr)), "top": np.asarray(tf), "bottom": np.asarray(bf), "top_count": r["top_count"],
+                "bottom_count": r["bottom_count"], "cut_rank": r["cut_rank"], "cut": part(slice(Qr, L)), "p_top": r["p_top"], "p_bottom": r["p_bottom"],
+                "n_above": r["n_above"], "n_below": r["n_below"], "probs": pr, "draws": S, "info": r["info"]}
 
     # ------------------------------------------------------------------ predict_projection
     def predict_projection(self, design, x_bart=None, x_bart0=None, X=None, X0=None, groups: Optional[Sequence[GroupTerm]] = None,
